@@ -11,6 +11,12 @@ Both run at snr -3 dB, where no codeblock converges, so every step does all 8 it
 final syndrome pass (worst case); `early_exit_*` repeat it at 1 dB.
 Synthetic data: random info bits -> GPU encoder -> BPSK + AWGN (torch RNG) — no datasets.
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps of the headline
+line alone and prints the result line.  `--full` adds everything else: the CPU baselines, the other
+schedule's config-3 line (`perf_mode`) and the `extras` (early exit, float32 flooding, encoder,
+latencies, BF / BP, configs 4 and 5).  `--dump-outputs DIR` writes what the headline's last timed
+step returned (decoded bits, status, iterations) as DIR/<name>.npy.
+
 Multi-GPU: one process per GPU (torch.distributed.run, or `--gpus N` alone, which starts the N
 rank processes itself), each decodes its own 4096-codeblock shard (weak scaling, no collective on
 the data path); timing = barrier + synchronize around the K steps, max over ranks.  Rank 0 prints
@@ -107,7 +113,7 @@ def valu_block(edge_rate, launch_s, kernel, B):
     return v
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -119,8 +125,15 @@ def parse():
     ap.add_argument("--snr", type=float, default=-3.0)
     ap.add_argument("--alpha", type=float, default=0.75)
     ap.add_argument("--L", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline line: the CPU baselines, the other "
+                         "schedule's config-3 line and the extras (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the headline decode's outputs of its last step "
+                         "(rank 0's shard) as DIR/<name>.npy: ck (a fixed, seeded sample of "
+                         f"{DUMP_ROWS} codeblocks' decoded bits), ck_rows (their indices), status, iters")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="budget of the bounded CPU-baseline sample (0 disables)")
+                    help="with --full: budget of the bounded CPU-baseline sample (0 disables)")
     ap.add_argument("--cpu-procs", type=int, default=0,
                     help="CPU-baseline processes (default: min(16, os.cpu_count()), the box's "
                          "CPU share per GPU)")
@@ -128,10 +141,37 @@ def parse():
                     help="process-group backend for N > 1 (nccl = RCCL; gloo only to rehearse the "
                          "multi-rank control flow with several ranks on one GPU)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements (early exit, flooding, encoder)")
+                    help="with --full: skip the secondary measurements (early exit, flooding, encoder)")
     ap.add_argument("--no-perf", action="store_true",
-                    help="time only the --headline line (skip the other schedule's config-3 line)")
-    return ap.parse_args()
+                    help="with --full: time only the --headline line (skip the other schedule's "
+                         "config-3 line)")
+    args = ap.parse_args(argv)
+    if not args.full:   # a plain run does only what the top-level figure needs
+        idle = ["--" + d.replace("_", "-") for d in ("cpu_seconds", "cpu_procs", "no_extras", "no_perf")
+                if getattr(args, d) != ap.get_default(d)]
+        if idle:
+            sys.stderr.write(f"bench.py: {', '.join(idle)} only trim a --full run; without --full "
+                             "nothing beside the headline line is measured\n")
+        args.cpu_seconds, args.no_extras, args.no_perf = 0.0, True, True
+    return args
+
+
+DUMP_ROWS, DUMP_SEED = 512, 20250
+
+
+def dump_outputs(path, out):
+    """Write a decode's outputs (ck int8 (B, N_FULL), status (B,), iters (B,)) as float32 .npy files
+    under `path`: status and iters whole, ck for min(B, DUMP_ROWS) codeblocks drawn once with a fixed
+    seed (the same rows in every run: 512 x 26112 float32 = 53 MB), their indices beside them."""
+    import numpy as np
+    ck, status, iters = out
+    B = ck.shape[0]
+    rows = np.sort(np.random.default_rng(DUMP_SEED).permutation(B)[:DUMP_ROWS])
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "ck.npy"), ck.cpu().numpy()[rows].astype(np.float32))
+    np.save(os.path.join(path, "ck_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "status.npy"), status.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "iters.npy"), iters.cpu().numpy().astype(np.float32))
 
 
 def make_llr(torch, enc, B, snr_db, seed, dev):
@@ -1061,8 +1101,12 @@ def main():
     lines = {}
     if args.headline == "reference" or not args.no_perf:
         lines["reference"] = bench_reference_precision(torch, dist, world, llr, out, args, cpu64)
+        if args.headline == "reference" and args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out)   # before another line reuses `out`
     if args.headline == "layered" or not args.no_perf:
         lines["layered"] = bench_perf_mode(torch, dist, world, llr, out, args, cpu_res)
+        if args.headline == "layered" and args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out)
     head = lines[args.headline]
     res = {
         "metric": "LDPC codeblocks/s + info-Gbit/s, BG1 Zc=384 NMS L=8, 1/2/4/8 MI355X",

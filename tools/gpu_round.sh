@@ -30,7 +30,7 @@ if has smoke; then
 fi
 if has bench; then
   echo "[gpu_round] bench"
-  timeout -k 10 420 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; die bench $?; }
+  timeout -k 10 420 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; die bench $?; }
   cat "$OUT/bench.json"
 fi
 if has trace; then
@@ -40,14 +40,14 @@ if has trace; then
   # warmups, so the decoder's average is over the launches behind the line's ms_per_step):
   # the headline (float64 flooding, reference-exact), then the float32 layered perf_mode line
   timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv \
-      -d "$OUT/prof_headline" -o run -- python -u "$ROOT/bench.py" --cpu-seconds 0 --no-extras --no-perf \
+      -d "$OUT/prof_headline" -o run -- python -u "$ROOT/bench.py" \
       > "$OUT/bench_headline_under_rocprof.json" 2> "$OUT/rocprof_headline.err" || { tail -20 "$OUT/rocprof_headline.err"; die trace $?; }
   timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv \
-      -d "$OUT/prof_layered" -o run -- python -u "$ROOT/bench.py" --cpu-seconds 0 --no-extras --no-perf --headline layered \
+      -d "$OUT/prof_layered" -o run -- python -u "$ROOT/bench.py" --headline layered \
       > "$OUT/bench_layered_under_rocprof.json" 2> "$OUT/rocprof_layered.err" || { tail -20 "$OUT/rocprof_layered.err"; die trace $?; }
   # everything (extras: encoder, flooding, config 4 / 5 chains): per-kernel table
   timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-      python -u "$ROOT/bench.py" --steps 10 --cpu-seconds 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err" \
+      python -u "$ROOT/bench.py" --full --steps 10 --cpu-seconds 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err" \
       || { tail -20 "$OUT/rocprof.err"; die trace $?; }
   cd "$ROOT"
   python tools/rocpd_summary.py "$OUT/prof_headline" --skip 3 > "$OUT/kernel_stats_headline.csv"
@@ -69,10 +69,10 @@ if has small; then
 fi
 if has rehearse; then
   echo "[gpu_round] 2-rank rehearsal (bench.py --gpus 2 --backend gloo: two ranks on one GPU)"
-  timeout -k 10 300 python -u bench.py --gpus 2 --backend gloo --no-extras --steps 10 --cpu-seconds 3 \
+  timeout -k 10 300 python -u bench.py --full --gpus 2 --backend gloo --no-extras --steps 10 --cpu-seconds 3 \
       > "$OUT/bench_w2_gloo.json" 2> "$OUT/bench_w2_gloo.err" || { tail -20 "$OUT/bench_w2_gloo.err"; die rehearse $?; }
   cat "$OUT/bench_w2_gloo.json"
-  timeout -k 10 120 python -u bench.py --gpus 8 --no-extras --cpu-seconds 0 > "$OUT/bench_w8_refused.json" 2> "$OUT/bench_w8_refused.err"
+  timeout -k 10 120 python -u bench.py --gpus 8 > "$OUT/bench_w8_refused.json" 2> "$OUT/bench_w8_refused.err"
   echo "bare --gpus 8 on one GPU: rc=$? $(cat "$OUT/bench_w8_refused.err")"
 fi
 if has probe; then

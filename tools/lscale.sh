@@ -9,6 +9,6 @@ for L in 1 8; do PROBE_L=$L timeout -k 10 120 python -u tools/probe.py flooding6
 PROBE_SNR=1 timeout -k 10 120 python -u tools/probe.py layered 4096 16384 >> $OUT/lscale.txt 2>&1
 grep -v amdgpu.ids $OUT/lscale.txt
 if [ "${WITH_BENCH:-0}" = 1 ]; then
-  timeout -k 10 420 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 3; }
+  timeout -k 10 420 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 3; }
   python -c "import json,sys; d=json.load(open('$OUT/bench.json')); print(d['value'], d['ms_per_step']); [print(k, v) for k, v in d.get('extras', {}).items()]" | cut -c1-400
 fi

@@ -13,6 +13,6 @@ grep -E "^(layered|flooding)|syndrome|prologue|store" $OUT/ts.txt
 for w in layered flooding64; do timeout -k 10 120 python -u tools/probe.py $w 4096 || exit 3; done 2>&1 | grep -v amdgpu.ids
 PROBE_SNR=1 timeout -k 10 120 python -u tools/probe.py layered 4096 2>&1 | grep -v amdgpu.ids
 if [ "${WITH_BENCH:-0}" = 1 ]; then
-  timeout -k 10 420 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 4; }
+  timeout -k 10 420 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 4; }
   python -c "import json; d=json.load(open('$OUT/bench.json')); print(d['value'], d['ms_per_step']); [print(k, str(v)[:300]) for k, v in d.get('extras', {}).items()]"
 fi
