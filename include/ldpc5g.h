@@ -340,6 +340,47 @@ int ldpc5g_demod_descramble(const void* sym, int32_t sym_dtype, int64_t ldsym,
                             int64_t ldw, int32_t T, int64_t nsym, int32_t mod, void* llr,
                             int32_t llr_dtype, int64_t ldllr, void* stream);
 
+/* ---- fused receive front end: symbols in, rate-recovered LLRs (or the decoded TB) out.
+ * The receive chain of a transport block (nr_pdsch.py:245-281 -> nr_dlsch_decode.py:62-106;
+ * UL-SCH: nr_pusch.py:194 -> nr_ulsch_decode.py:63-89) demodulates (nr_Demodulation.py:12-46), descrambles
+ * (nr_pdsch.py:268-274), then rate-recovers every codeblock (nr_ldpc_raterecover.py:25-64) and
+ * combines it with the HARQ buffer (nr_dlsch_decode.py:73-88).  ldpc5g_sch_demod_raterecover does
+ * all of that in ONE launch: the workgroup of a codeblock demodulates the codeblock's own E/Qm
+ * symbols into LDS and rate-recovers from there, so the demodulated LLRs never go to memory.  The
+ * result is, bit for bit, ldpc5g_demod_descramble followed by ldpc5g_sch_raterecover:
+ *   sym [T][ldsym] complex64 (sym_dtype LDPC5G_F32) / complex128 (LDPC5G_F64) and noise_var
+ *   [T][ldnv] float32, nsym = cfg->E_total / cfg->Qm of each used; prbs NULL (no descrambling) or
+ *   the packed words [T][ldw] of ldpc5g_prbs (>= E_total bits); mod as ldpc5g_demod_descramble, with
+ *   |mod| == cfg->Qm (mod distinguishes BPSK from pi/2-BPSK, whose odd/even rule follows the
+ *   symbol's index in the TB row, demod_pi2_bpsk.py:11-12); harq_in / llr_dn / dn_dtype as
+ *   ldpc5g_sch_raterecover (harq_in may be llr_dn itself).
+ * The demodulated LLRs are float32 as nr_Demodulation.py stores them — float64 for BPSK on
+ * complex128 symbols (demod_bpsk.py:9 stores nothing).  A configuration with a codeblock whose E
+ * LLRs exceed the 64 KiB LDS stage (ldpc5g_sch_rx_scratch_elems != 0) needs llr_ws: scratch
+ * [T][ldws] of that LLR type, ldws >= E_total, through which the call runs the two separate
+ * kernels (same result); without it the call fails with LDPC5G_ESIZE.  llr_ws may be NULL
+ * otherwise.  Asynchronous on `stream`. */
+int ldpc5g_sch_demod_raterecover(const void* sym, int32_t sym_dtype, int64_t ldsym,
+                                 const float* noise_var, int64_t ldnv, const uint32_t* prbs,
+                                 int64_t ldw, int32_t mod, const ldpc5g_sch_cfg_t* cfg, int32_t T,
+                                 const void* harq_in, void* llr_dn, int32_t dn_dtype, void* llr_ws,
+                                 int64_t ldws, void* stream);
+/* Elements per TB row of the llr_ws scratch the configuration needs (E_total), 0 when every
+ * codeblock fits the stage, or a negative error code.  No reference counterpart. */
+int64_t ldpc5g_sch_rx_scratch_elems(const ldpc5g_sch_cfg_t* cfg, int32_t mod, int32_t sym_dtype);
+/* The receive chain from symbols to transport block (nr_pdsch.py:245-281 -> DLSCHDecode
+ * nr_dlsch_decode.py:13-110 / ULSCH_decoding nr_ulsch_decode.py:13-110) with the min-sum decoder:
+ * ldpc5g_sch_demod_raterecover -> ldpc5g_decode_ms -> ldpc5g_sch_tb_check, chained as in
+ * ldpc5g_sch_decode (same ck / status / iters / tbblk / cb_crc_ok / tb_rem / tb_ok).
+ * Asynchronous on `stream`. */
+int ldpc5g_sch_rx_decode(const void* sym, int32_t sym_dtype, int64_t ldsym, const float* noise_var,
+                         int64_t ldnv, const uint32_t* prbs, int64_t ldw, int32_t mod,
+                         const ldpc5g_sch_cfg_t* cfg, int32_t T, const void* harq_in, void* llr_dn,
+                         int32_t dn_dtype, void* llr_ws, int64_t ldws, int8_t* ck, uint8_t* status,
+                         int32_t* iters, int32_t L, double alpha, double beta, int32_t schedule,
+                         int8_t* tbblk, int64_t ldb, uint8_t* cb_crc_ok, uint32_t* tb_rem,
+                         uint8_t* tb_ok, void* stream);
+
 /* ================================================ gather records (multi-GPU)
  * Record r (a row of rec, stride ldr bytes) = the nbits int8 bits of row r of `bits` (values 0/1)
  * packed in np.packbits order (bit i -> byte i/8, bit 7 - i%8, tail zero-padded), then

@@ -83,6 +83,18 @@ SIGNATURES = {
                                      _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_double,
                                      _c.c_double, _c.c_int32, _c.c_void_p, _c.c_int64,
                                      _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "ldpc5g_sch_demod_raterecover": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p,
+                                                _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
+                                                _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p,
+                                                _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "ldpc5g_sch_rx_scratch_elems": (_c.c_int64, [_c.c_void_p, _c.c_int32, _c.c_int32]),
+    "ldpc5g_sch_rx_decode": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p,
+                                        _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
+                                        _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p,
+                                        _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                        _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_double,
+                                        _c.c_double, _c.c_int32, _c.c_void_p, _c.c_int64,
+                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "ldpc5g_sch_multi_sizes": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_void_p]),
     "ldpc5g_sch_encode_multi": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
                                            _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p,

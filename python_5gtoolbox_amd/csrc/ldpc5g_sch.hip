@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "ldpc5g_common.h"
+#include "ldpc5g_demod.h"
 
 namespace ldpc5g_impl {
 namespace {
@@ -621,6 +622,111 @@ __global__ __launch_bounds__(kRrNT) void raterecover_kernel(const Tin* __restric
     }
 }
 
+// The fused receive front end: soft demodulation (nr_Demodulation.py:12-46, demod_*.py) + LLR
+// descrambling (nr_pdsch.py:268-274) + rate recovery + HARQ combining of codeblock (t, c) in one
+// workgroup, the chain nr_pdsch.py:245-281 -> nr_dlsch_decode.py:62-88.  Every Er is a multiple of
+// NL*Qm, so the codeblock's E LLRs are those of its own E/Qm symbols m = cb_goff/Qm + r of the
+// TB row: a thread demodulates symbol r and writes its Qm LLRs straight into the de-interleaved
+// LDS planes lk[q*EQ + r] (consecutive r -> consecutive LDS addresses), the layout
+// raterecover_kernel's stage holds, so the LLRs never go to HBM.  The whole codeblock is staged
+// (the launcher sends configurations with a larger row through the two separate kernels), and the
+// output is one position-major pass: lk[k] read at consecutive k, 16-byte stores.
+// Tl: the type the reference stores its LLRs in — float32, or float64 for BPSK on complex128.
+#ifndef LDPC5G_RX_NT
+#define LDPC5G_RX_NT 512
+#endif
+constexpr int kRxNT = LDPC5G_RX_NT;
+// largest staged codeblock: 64 KiB of LLRs.  LDS per launch = its largest codeblock, so a CU
+// (160 KiB) holds 4 workgroups up to 40 KiB rows (the 32-waves-per-CU cap), 3 up to 53.3 KiB, 2 above
+constexpr int kRxStageBytes = 64 * 1024;
+
+template <int QM, bool PI2, typename Tsym, typename Tout>
+__global__ __launch_bounds__(kRxNT) void demod_raterecover_kernel(const Tsym* __restrict__ sym, int64_t ldsym,
+                                                                  const float* __restrict__ nvar, int64_t ldnv,
+                                                                  const uint32_t* __restrict__ prbs, int64_t ldw,
+                                                                  double A, SchDev s0, const Tout* harq,
+                                                                  Tout* out) {
+    using C = decltype(Tsym{}.x);
+    using Tl = std::conditional_t<QM == 1 && !PI2 && sizeof(C) == 8, double, float>;
+    __shared__ double red[kRxNT / 64];
+    extern __shared__ __align__(16) unsigned char rx_smem[];
+    Tl* lk = (Tl*)rx_smem;
+    const RowGeo rg = row_geo(blockIdx.x, s0, nullptr, nullptr, 0);
+    const SchDev& s = rg.s;
+    const int t = rg.t, c = rg.c;
+    const int E = cb_E(s, c), EQ = E / QM;
+    const int64_t goff = cb_goff(s, c), m0 = goff / QM;   // first bit / symbol of the codeblock in the TB row
+    const Tsym* ys = sym + (int64_t)t * ldsym + m0;
+    const float* nvs = nvar + (int64_t)t * ldnv + m0;
+    const uint32_t* w = prbs ? prbs + (int64_t)t * ldw : nullptr;
+    double m = 0.0;
+    for (int r = threadIdx.x; r < EQ; r += kRxNT) {
+        const Tsym y = ys[r];
+        const C nv = (C)nvs[r];
+        const uint32_t cb = w ? prbs_bits(w, goff + (int64_t)r * QM, QM) : 0u;
+        Tl v[QM];
+        demod_symbol<QM>((C)y.x, (C)y.y, nv, A, PI2 && ((m0 + r) & 1), v);   // pi/2: parity in the TB row
+#pragma unroll
+        for (int q = 0; q < QM; ++q) {   // descrambling: LLR * (1 - 2c), an exact sign flip
+            const Tl x = flip_sign(v[q], (cb >> q) & 1u);
+            lk[q * EQ + r] = x;
+            m = fmax(m, fabs((double)x));
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();   // the partial maxima and every staged LLR
+    m = red[0];
+#pragma unroll
+    for (int wv = 1; wv < kRxNT / 64; ++wv) m = fmax(m, red[wv]);
+    const double mx = m * 10.0;
+    const int qE = E / s.size, rE = E - qE * s.size;   // visits of rank rr: qE + (rr < rE)
+    const int64_t row = rg.dn_row;
+    Tout* orow = out + row;
+    // position p of the row (nr_ldpc_raterecover.py:25-64 + nr_dlsch_decode.py:73-88), in float64
+    auto value = [&](int p) -> double {
+        double v = 0.0;
+        if (p >= s.f0 && p < s.f0 + s.F) {
+            v = mx;
+        } else if (p < s.Ncb) {
+            int rr = (p < s.f0 ? p : p - s.Fin) - s.start;   // rank in the circular order from k0
+            if (rr < 0) rr += s.size;
+            if (rr < E) {
+                const int cnt = qE + (rr < rE ? 1 : 0);
+                double acc = 0.0;
+                for (int j = 0; j < cnt; ++j) acc += (double)lk[rr + j * s.size];
+                v = cnt == 1 ? acc : acc / (double)cnt;   // x / 1.0 == x: skip the f64 divide
+            }
+        }
+        if (harq) {
+            const double h = (double)harq[row + p];
+            v = (v == 0.0 || h == 0.0) ? v + h : (v + h) / 2.0;
+        }
+        return v;
+    };
+    const bool vec = ((uintptr_t)orow & 15) == 0;
+    for (int p0 = 4 * (int)threadIdx.x; p0 < s.N; p0 += 4 * kRxNT) {
+        Tout v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = p0 + q < s.N ? (Tout)value(p0 + q) : Tout(0);
+        if (vec && p0 + 4 <= s.N) {
+            if constexpr (sizeof(Tout) == 4) {
+                using f4 = float __attribute__((ext_vector_type(4)));
+                *(f4*)(orow + p0) = f4{v[0], v[1], v[2], v[3]};
+            } else {
+                using d2 = double __attribute__((ext_vector_type(2)));
+                *(d2*)(orow + p0) = d2{v[0], v[1]};
+                *(d2*)(orow + p0 + 2) = d2{v[2], v[3]};
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (p0 + q < s.N) orow[p0 + q] = v[q];
+        }
+    }
+}
+
 // TB reassembly + checks (nr_dlsch_decode.py:93-106) for codeblock (t, c), one pass over
 // ck[0:cbz]: the TB CRC share crc(seg) * x^((C-1-c) cbz), XORed into tbrem[t]; CRC24B over
 // ck[0:K_apo] when C > 1 (cb_ok = remainder 0) as crc24B(ck[0:cbz]) x^24 + crc24B(ck[cbz:K_apo]);
@@ -723,6 +829,33 @@ int launch_raterecover(dim3 grid, const void* llr, int llr_dtype, int64_t ldg, c
     else
         raterecover_go<double, double>(grid, llr, ldg, s, gv, rm, harq_in, llr_dn, max_cb_E, st);
     return check_hip(hipGetLastError(), "raterecover launch");
+}
+
+// ---- fused receive front end (demod_raterecover_kernel)
+// bytes of one staged LLR: float32, float64 for BPSK on complex128 symbols (demod_bpsk.py:9)
+inline int rx_llr_dtype(int mod, int sym_dtype) { return mod == 1 && sym_dtype == LDPC5G_F64 ? LDPC5G_F64 : LDPC5G_F32; }
+inline size_t rx_llr_bytes(int mod, int sym_dtype) { return rx_llr_dtype(mod, sym_dtype) == LDPC5G_F64 ? 8 : 4; }
+inline bool rx_staged(const SchDev& s, int mod, int sym_dtype) {
+    return (size_t)std::max(s.E_lo, s.E_hi) * rx_llr_bytes(mod, sym_dtype) <= (size_t)kRxStageBytes;
+}
+
+template <typename Tsym, typename Tout>
+void demod_raterecover_go(int mod, dim3 grid, size_t lds, hipStream_t st, const void* sym, int64_t ldsym,
+                          const float* nv, int64_t ldnv, const uint32_t* prbs, int64_t ldw, double A,
+                          const SchDev& s, const void* harq_in, void* llr_dn) {
+#define LDPC5G_RX(QM, PI2)                                                                                       \
+    hipLaunchKernelGGL((demod_raterecover_kernel<QM, PI2, Tsym, Tout>), grid, dim3(kRxNT), lds, st, (const Tsym*)sym, \
+                       ldsym, nv, ldnv, prbs, ldw, A, s, (const Tout*)harq_in, (Tout*)llr_dn)
+    switch (mod) {
+        case -1: LDPC5G_RX(1, true); break;
+        case 1: LDPC5G_RX(1, false); break;
+        case 2: LDPC5G_RX(2, false); break;
+        case 4: LDPC5G_RX(4, false); break;
+        case 6: LDPC5G_RX(6, false); break;
+        case 8: LDPC5G_RX(8, false); break;
+        default: LDPC5G_RX(10, false); break;
+    }
+#undef LDPC5G_RX
 }
 
 // Host side of a multi-configuration batch: validated per-TB geometry (workspace offsets in TB
@@ -945,6 +1078,80 @@ int ldpc5g_sch_decode(const void* llr, int32_t llr_dtype, int64_t ldg, const ldp
                       int32_t schedule, int8_t* tbblk, int64_t ldb, uint8_t* cb_crc_ok,
                       uint32_t* tb_rem, uint8_t* tb_ok, void* stream) {
     if (int rc = ldpc5g_sch_raterecover(llr, llr_dtype, ldg, cfg, T, harq_in, llr_dn, dn_dtype, stream)) return rc;
+    if (T == 0) return LDPC5G_OK;
+    const int Nf = (cfg->bgn == 1 ? 68 : 52) * cfg->Zc;
+    if (int rc = ldpc5g_decode_ms(llr_dn, dn_dtype, ck, status, iters, T * cfg->C, cfg->bgn, cfg->Zc, L,
+                                  alpha, beta, schedule, LDPC5G_RATE_MATCHED, cfg->N, Nf, stream))
+        return rc;
+    return ldpc5g_sch_tb_check(ck, Nf, cfg, T, tbblk, ldb, cb_crc_ok, tb_rem, tb_ok, stream);
+}
+
+int64_t ldpc5g_sch_rx_scratch_elems(const ldpc5g_sch_cfg_t* cfg, int32_t mod, int32_t sym_dtype) {
+    clear_error();
+    SchDev s;
+    if (int rc = sch_dev(cfg, &s)) return rc;
+    if (!mod_ok(mod) || (mod < 0 ? 1 : mod) != s.Qm) return fail(LDPC5G_ESIZE, "modulation %d does not match cfg Qm=%d", mod, s.Qm);
+    if (sym_dtype != LDPC5G_F32 && sym_dtype != LDPC5G_F64) return fail(LDPC5G_ESIZE, "bad symbol dtype %d", sym_dtype);
+    return rx_staged(s, mod, sym_dtype) ? 0 : sch_total_E(s);
+}
+
+int ldpc5g_sch_demod_raterecover(const void* sym, int32_t sym_dtype, int64_t ldsym, const float* noise_var,
+                                 int64_t ldnv, const uint32_t* prbs, int64_t ldw, int32_t mod,
+                                 const ldpc5g_sch_cfg_t* cfg, int32_t T, const void* harq_in, void* llr_dn,
+                                 int32_t dn_dtype, void* llr_ws, int64_t ldws, void* stream) {
+    clear_error();
+    SchDev s;
+    if (int rc = sch_dev(cfg, &s)) return rc;
+    if (!mod_ok(mod)) return fail(LDPC5G_ESIZE, "modulation %d (1 BPSK, -1 pi/2-BPSK, 2/4/6/8/10 QPSK..1024QAM)", mod);
+    if ((mod < 0 ? 1 : mod) != s.Qm) return fail(LDPC5G_ESIZE, "modulation %d does not match cfg Qm=%d", mod, s.Qm);
+    if (sym_dtype != LDPC5G_F32 && sym_dtype != LDPC5G_F64) return fail(LDPC5G_ESIZE, "bad symbol dtype %d", sym_dtype);
+    if (dn_dtype != LDPC5G_F32 && dn_dtype != LDPC5G_F64) return fail(LDPC5G_ESIZE, "bad llr_dn dtype %d", dn_dtype);
+    const int64_t Et = sch_total_E(s), nsym = Et / s.Qm;
+    if (T < 0) return fail(LDPC5G_ESIZE, "bad sizes T=%d", T);
+    if (T > 1 && (ldsym < nsym || ldnv < nsym || (prbs && ldw < (Et + 31) / 32)))
+        return fail(LDPC5G_ESIZE, "bad strides ldsym=%lld ldnv=%lld ldw=%lld (%lld symbols per TB)", (long long)ldsym,
+                    (long long)ldnv, (long long)ldw, (long long)nsym);
+    if (T == 0) return LDPC5G_OK;
+    const int wdt = rx_llr_dtype(mod, sym_dtype);
+    const bool staged = rx_staged(s, mod, sym_dtype);
+    if (!staged && !llr_ws)
+        return fail(LDPC5G_ESIZE, "a codeblock of E=%d LLRs (%zu bytes) exceeds the %d-byte LDS stage of the fused "
+                    "front end: pass llr_ws scratch ([T][>= %lld] %s)", std::max(s.E_lo, s.E_hi),
+                    (size_t)std::max(s.E_lo, s.E_hi) * rx_llr_bytes(mod, sym_dtype), kRxStageBytes, (long long)Et,
+                    wdt == LDPC5G_F64 ? "float64" : "float32");
+    if (!sym || !noise_var || !llr_dn) return fail(LDPC5G_ESIZE, "null buffer");
+    if (!staged) {
+        // a codeblock too large for the LDS stage: the two separate kernels through the scratch
+        if (T > 1 && ldws < Et) return fail(LDPC5G_ESIZE, "bad stride ldws=%lld (E_total %lld)", (long long)ldws, (long long)Et);
+        if (int rc = ldpc5g_demod_descramble(sym, sym_dtype, ldsym, noise_var, ldnv, prbs, ldw, T, nsym, mod, llr_ws,
+                                             wdt, ldws, stream))
+            return rc;
+        return ldpc5g_sch_raterecover(llr_ws, wdt, ldws, cfg, T, harq_in, llr_dn, dn_dtype, stream);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const double A = 1.0 / sqrt((double)mod_scale(s.Qm));   // A = 1/math.sqrt(scale) (demod_*.py)
+    const size_t lds = (size_t)std::max(s.E_lo, s.E_hi) * rx_llr_bytes(mod, sym_dtype);
+    const dim3 grid(T * s.C);
+    if (sym_dtype == LDPC5G_F32 && dn_dtype == LDPC5G_F32)
+        demod_raterecover_go<float2, float>(mod, grid, lds, st, sym, ldsym, noise_var, ldnv, prbs, ldw, A, s, harq_in, llr_dn);
+    else if (sym_dtype == LDPC5G_F32)
+        demod_raterecover_go<float2, double>(mod, grid, lds, st, sym, ldsym, noise_var, ldnv, prbs, ldw, A, s, harq_in, llr_dn);
+    else if (dn_dtype == LDPC5G_F32)
+        demod_raterecover_go<double2, float>(mod, grid, lds, st, sym, ldsym, noise_var, ldnv, prbs, ldw, A, s, harq_in, llr_dn);
+    else
+        demod_raterecover_go<double2, double>(mod, grid, lds, st, sym, ldsym, noise_var, ldnv, prbs, ldw, A, s, harq_in, llr_dn);
+    return check_hip(hipGetLastError(), "demod_raterecover launch");
+}
+
+int ldpc5g_sch_rx_decode(const void* sym, int32_t sym_dtype, int64_t ldsym, const float* noise_var, int64_t ldnv,
+                         const uint32_t* prbs, int64_t ldw, int32_t mod, const ldpc5g_sch_cfg_t* cfg, int32_t T,
+                         const void* harq_in, void* llr_dn, int32_t dn_dtype, void* llr_ws, int64_t ldws,
+                         int8_t* ck, uint8_t* status, int32_t* iters, int32_t L, double alpha, double beta,
+                         int32_t schedule, int8_t* tbblk, int64_t ldb, uint8_t* cb_crc_ok, uint32_t* tb_rem,
+                         uint8_t* tb_ok, void* stream) {
+    if (int rc = ldpc5g_sch_demod_raterecover(sym, sym_dtype, ldsym, noise_var, ldnv, prbs, ldw, mod, cfg, T, harq_in,
+                                              llr_dn, dn_dtype, llr_ws, ldws, stream))
+        return rc;
     if (T == 0) return LDPC5G_OK;
     const int Nf = (cfg->bgn == 1 ? 68 : 52) * cfg->Zc;
     if (int rc = ldpc5g_decode_ms(llr_dn, dn_dtype, ck, status, iters, T * cfg->C, cfg->bgn, cfg->Zc, L,

@@ -5,6 +5,8 @@ one configuration — the C-ABI entry points ldpc5g_sch_* of include/ldpc5g.h.
     crc_rows(bits[R, >=n], poly, nbits=None) -> rem[R] uint32             (crc.py:4-88)
     sch_encode_batch(trblk[T, A], cfg) -> g[T, E_total]                    (nr_dlsch.py:12-74)
     sch_decode_batch(llr[T, E_total], cfg, L, ...) -> SchDecodeResult      (nr_dlsch_decode.py)
+    sch_demod_raterecover_batch(sym[T, E_total/Qm], noise_var, mod, cfg, ...) -> llr_dn[T*C, N]
+    sch_rx_batch(sym, noise_var, mod, cfg, L, ...) -> SchDecodeResult      (nr_pdsch.py:245-281)
 
 Device tensors in, device tensors out, everything asynchronous on the current stream; torch only
 allocates the buffers.  The per-transport-block drop-ins (nr_dlsch.DLSCHEncode,
@@ -87,6 +89,7 @@ class SchWorkspace:
         self.tb_rem = t.empty((T,), dtype=t.int32, device=device)
         self.tb_ok = t.empty((T,), dtype=t.uint8, device=device)
         self.llr_dn = {}
+        self.rx_llr = {}
         self.device = device
 
     def dn_buf(self, dtype, cfg):
@@ -94,6 +97,14 @@ class SchWorkspace:
         if dtype not in self.llr_dn:
             self.llr_dn[dtype] = t.empty((self.T * cfg.C, cfg.N), dtype=dtype, device=self.device)
         return self.llr_dn[dtype]
+
+    def rx_scratch(self, dtype, cfg):
+        """Demodulated-LLR scratch (T, E_total) of the fused receive front end, for configurations
+        whose codeblocks do not fit its LDS stage; allocated on first use."""
+        t = _lib.torch()
+        if dtype not in self.rx_llr:
+            self.rx_llr[dtype] = t.empty((self.T, max(cfg.E_total, 1)), dtype=dtype, device=self.device)
+        return self.rx_llr[dtype]
 
 
 def _dtype_id(t, dt):
@@ -230,6 +241,109 @@ def sch_decode_batch(llr, cfg, L, algo="min-sum", alpha=1.0, beta=0.0, schedule=
         llr_dn = sch_raterecover_batch(llr, cfg, harq_in, dn_dtype, ws)
         nr_decode_ldpc_batch(llr_dn, cfg.Zc, cfg.bgn, L, algo, alpha, beta, "flooding",
                              out=(ws.dec_ck, ws.status, ws.iters), rate_matched=True)
+        sch_tb_check_batch(ws.dec_ck, cfg, T, ws)
+    return SchDecodeResult(ws.tb_ok, ws.tbblk, llr_dn, ws.dec_ck, ws.status, ws.iters, ws.cb_ok,
+                           ws.tb_rem)
+
+
+# ------------------------------------------------------------ fused receive front end
+def _rx_args(sym, noise_var, mod, cfg, cinit, words, harq_in, dn_dtype, ws):
+    """Checked inputs of the fused front end -> (T, workspace, the 15 C arguments before `stream`,
+    llr_dn, the temporaries the launch reads: kept alive by the caller until it is queued)."""
+    from . import phy
+    t = _lib.require_gpu()
+    assert sym.dim() == 2 and sym.dtype in (t.complex64, t.complex128) and sym.stride(1) == 1
+    assert phy.bits_per_symbol(mod) == cfg.Qm, "modulation does not match cfg.Qm"
+    T, nsym = sym.shape[0], cfg.E_total // cfg.Qm
+    assert sym.shape[1] >= nsym
+    nv = noise_var if noise_var.dtype == t.float32 and noise_var.stride(1) == 1 else \
+        noise_var.to(t.float32).contiguous()
+    assert nv.dim() == 2 and nv.shape[0] == T and nv.shape[1] >= nsym
+    w = words if words is not None else \
+        (phy.prbs_words(cinit, cfg.E_total) if cinit is not None else None)
+    if w is not None:
+        assert w.dim() == 2 and w.shape[0] == T and w.stride(1) == 1 and w.shape[1] * 32 >= cfg.E_total
+    ws = ws or SchWorkspace(cfg, T, sym.device)
+    out = ws.dn_buf(dn_dtype, cfg)
+    if harq_in is not None:
+        assert harq_in.dtype == dn_dtype and harq_in.shape == out.shape and harq_in.is_contiguous()
+    sdt = _lib.F32 if sym.dtype == t.complex64 else _lib.F64
+    need = _lib.lib().ldpc5g_sch_rx_scratch_elems(_lib.ctypes.byref(cfg), int(mod), sdt)
+    _lib.check(int(min(need, 0)))
+    scr = None
+    if need:   # a codeblock too large for the LDS stage: the two kernels through this scratch
+        scr = ws.rx_scratch(t.float64 if int(mod) == 1 and sdt == _lib.F64 else t.float32, cfg)
+    args = (_lib.ptr(sym), sdt, sym.stride(0), _lib.ptr(nv), nv.stride(0),
+            _lib.ptr(w) if w is not None else None, w.stride(0) if w is not None else 0, int(mod),
+            _lib.ctypes.byref(cfg), T, _lib.ptr(harq_in) if harq_in is not None else None,
+            _lib.ptr(out), _dtype_id(t, dn_dtype), _lib.ptr(scr) if scr is not None else None,
+            scr.stride(0) if scr is not None else 0)
+    return T, ws, args, out, (nv, w)
+
+
+def sch_demod_raterecover_batch(sym, noise_var, mod, cfg, cinit=None, words=None, harq_in=None,
+                                dn_dtype=None, ws=None):
+    """Soft demodulation + descrambling + rate recovery + HARQ combining in one launch
+    (ldpc5g_sch_demod_raterecover): sym (T, >= E_total/Qm) complex64/128 and noise_var (same
+    shape, float32) device tensors, mod a phy.MOD_ID value with |mod| == cfg.Qm, cinit (T,) or
+    precomputed phy.prbs_words `words` (neither: no descrambling) -> llr_dn (T*C, N) of dn_dtype
+    (default float64 for complex128 symbols, float32 for complex64).  Bit for bit
+    sch_raterecover_batch(phy.demod_descramble(...)), without the LLRs' trip through memory."""
+    t = _lib.require_gpu()
+    dn_dtype = dn_dtype or (t.float64 if sym.dtype == t.complex128 else t.float32)
+    T, ws, args, out, keep = _rx_args(sym, noise_var, mod, cfg, cinit, words, harq_in, dn_dtype, ws)
+    with t.cuda.device(sym.device):
+        _lib.check(_lib.lib().ldpc5g_sch_demod_raterecover(*args, _lib.stream_ptr(sym.device)))
+    return out
+
+
+def sch_rx_batch(sym, noise_var, mod, cfg, L, algo="min-sum", alpha=1.0, beta=0.0,
+                 schedule="flooding", cinit=None, words=None, harq_in=None, dn_dtype=None, ws=None,
+                 fused=True):
+    """The receive chain of T transport blocks from equalised symbols to TB bits (the tail of the
+    reference's RX_process, nr_pdsch.py:245-281, and DLSCHDecode / ULSCH_decoding): demodulate,
+    descramble, rate-recover (+ HARQ), decode, CRC.  Arguments as sch_demod_raterecover_batch and
+    sch_decode_batch; dn_dtype defaults to float64 for 'flooding' and float32 for 'layered'.
+    fused=True runs the front end as one launch (ldpc5g_sch_rx_decode); fused=False runs
+    phy.demod_descramble then sch_decode_batch.  Both give the same SchDecodeResult."""
+    from . import phy
+    t = _lib.require_gpu()
+    assert algo in ["BF", "BP", "min-sum"]
+    sparse = algo == "min-sum" and not beta >= 0   # see sch_decode_batch
+    if sparse:
+        assert schedule == "flooding", "beta < 0 decodes with the float64 flooding sparse kernel only"
+        assert dn_dtype in (None, t.float64), "beta < 0: rate recovery must be float64 (dn_dtype)"
+    dn_dtype = dn_dtype or (t.float32 if schedule == "layered" else t.float64)
+    if not fused:
+        nsym = cfg.E_total // cfg.Qm
+        f64 = int(mod) == 1 and sym.dtype == t.complex128   # demod_bpsk.py:9 keeps float64
+        llr = phy.demod_descramble(sym[:, :nsym], noise_var[:, :nsym], mod, cinit, words,
+                                   llr_dtype=t.float64 if f64 else None)
+        return sch_decode_batch(llr, cfg, L, algo, alpha, beta, schedule, harq_in, dn_dtype, ws)
+    if algo == "min-sum" and not sparse:
+        T, ws, args, llr_dn, keep = _rx_args(sym, noise_var, mod, cfg, cinit, words, harq_in, dn_dtype, ws)
+        sched = {"flooding": _lib.FLOODING, "layered": _lib.LAYERED}[schedule]
+        with t.cuda.device(sym.device):
+            _lib.check(_lib.lib().ldpc5g_sch_rx_decode(
+                *args, _lib.ptr(ws.dec_ck), _lib.ptr(ws.status), _lib.ptr(ws.iters), int(L),
+                float(alpha), float(beta), sched, _lib.ptr(ws.tbblk), ws.tbblk.stride(0),
+                _lib.ptr(ws.cb_ok), _lib.ptr(ws.tb_rem), _lib.ptr(ws.tb_ok),
+                _lib.stream_ptr(sym.device)))
+    else:
+        T = sym.shape[0]
+        ws = ws or SchWorkspace(cfg, T, sym.device)
+        llr_dn = sch_demod_raterecover_batch(sym, noise_var, mod, cfg, cinit, words, harq_in, dn_dtype, ws)
+        if sparse:
+            from .nr_ldpc_decode import SparseGraph, _sparse_graph, decode_ldpc_batch
+            x = t.zeros((T * cfg.C, cfg.N + 2 * cfg.Zc), dtype=t.float64, device=sym.device)
+            x[:, 2 * cfg.Zc:] = llr_dn   # punctured systematic columns: LLR 0 (nr_ldpc_decode.py:43)
+            g = _sparse_graph(("bg", cfg.bgn, cfg.Zc),
+                              lambda: SparseGraph.from_base_graph(cfg.bgn, cfg.Zc, sym.device), sym.device)
+            decode_ldpc_batch(x, g, L, algo, alpha, beta, out=(ws.dec_ck, ws.status, ws.iters))
+        else:
+            from .nr_ldpc_decode import nr_decode_ldpc_batch
+            nr_decode_ldpc_batch(llr_dn, cfg.Zc, cfg.bgn, L, algo, alpha, beta, "flooding",
+                                 out=(ws.dec_ck, ws.status, ws.iters), rate_matched=True)
         sch_tb_check_batch(ws.dec_ck, cfg, T, ws)
     return SchDecodeResult(ws.tb_ok, ws.tbblk, llr_dn, ws.dec_ck, ws.status, ws.iters, ws.cb_ok,
                            ws.tb_rem)
