@@ -243,6 +243,17 @@ constexpr bool fr_item(int H, int i, int k) {
     if (j < 2 || j >= BGT<BG>::KC) return false;
     return kFrPlan<BG>.lds[i] ? kFrPlan<BG>.eh[i][k] == H : kFrPlan<BG>.owner[i] == H;
 }
+// does row i hold a punctured column (0 or 1); the lowest row without one that holds column j
+// (-1: none).  The peeled first iteration (ldpc5g_dec_frame_iter.h, FIRST) splits the rows so.
+template <int BG>
+constexpr bool fr_punct(int i) { return kFrPlan<BG>.kc[0][i] >= 0 || kFrPlan<BG>.kc[1][i] >= 0; }
+template <int BG>
+constexpr int fr_first_free(int j) {
+    for (int i = 0; i < BGT<BG>::MB; ++i)
+        for (int e = BGT<BG>::RS[i]; !fr_punct<BG>(i) && e < BGT<BG>::RS[i + 1]; ++e)
+            if (BGT<BG>::COL[e] == j) return i;
+    return -1;
+}
 // ((e mod Zc) * 8) for 0 <= c < Zc: byte offset of entry (s + c) mod Zc from the thread's own s*8
 // and s*8 - Zc*8 (the smaller as unsigned is the valid one)
 __device__ __forceinline__ uint32_t fr_rot(uint32_t sb, uint32_t sbw, int c) {
@@ -374,7 +385,8 @@ __device__ __forceinline__ void frame_body(
         }
     };
 
-    // ---- load: LQ = LLRin (:94), punctured columns 0 (:43); LDS state 0; wrap table; flags.
+    // ---- load: LQ = LLRin (:94), punctured columns 0 (:43); LDS state 0 (unless the
+    // first iteration runs peeled and writes it, see `peel`); wrap table; flags.
     // KDEAD: each thread also loads its entry of its half's extension rows (in the row's frame:
     // together all Zc entries of every row); a wave's ballots give one word (bit p: xlist row p
     // live) at the flags' offset 16 + 4 * wave, ORed per half after the prologue's barrier.
@@ -411,7 +423,18 @@ __device__ __forceinline__ void frame_body(
         }
         if (KDEAD && (t & 63) == 0) *(lds_u32*)(uintptr_t)(uint32_t)(kFrPlan<BG>.fl_b + 16 + (t >> 6) * 4) = wm;
     }
-    for (int w = t; w < kFrPlan<BG>.nls * Z; w += kFrThreads) {
+    // the first iteration runs peeled (FIRST) when columns 0 and 1 are punctured and the message
+    // alpha * max(0 - beta, 0) of a zero minimum is +-0 (any finite alpha).  It writes every
+    // state field itself, so the LDS state needs no zero fill then.  Not in the KDEAD kernels:
+    // a third copy of the iteration beside their two spills VGPRs to scratch.
+    T zmsg = T(0);
+    if constexpr (OFS) {
+        zmsg = zmsg - beta;
+        zmsg = zmsg > T(0) ? zmsg : T(0);
+    }
+    // L = 0 runs no iteration at all: the final pass then reads the zero state filled here.
+    const bool peel = !KDEAD && L >= 1 && pc == 2 && alpha * zmsg == T(0);
+    for (int w = t; !peel && w < kFrPlan<BG>.nls * Z; w += kFrThreads) {
         V2<T> v;
         v.x = T(0), v.y = T(0);
         *(lds_V2*)(uintptr_t)(uint32_t)(kFrPlan<BG>.st_b + w * 16) = v;
@@ -419,7 +442,7 @@ __device__ __forceinline__ void frame_body(
     }
     // wrap table: entry e < 2*Zc holds (e mod Zc) * 8
     *(lds_u32*)(uintptr_t)(uint32_t)(kFrPlan<BG>.tbl_b + t * 4) = (uint32_t)s * 8u;
-    if (t == 0) *flagA = 0, *anyf = 0;
+    if (t == 0) *flagA = 0, *anyf = 0, flagA[2] = 0;   // flagA[2]: the peeled iteration's syndrome flag
     lds_barrier();
     uint64_t live_x = ~0ull;
     if constexpr (KDEAD) {
@@ -446,7 +469,15 @@ __device__ __forceinline__ void frame_body(
     bool active = true;
     uint64_t hdx_keep = 0;   // extension decisions of a codeblock decided by the syndrome test
     int it = 0;
-    if constexpr (KDEAD) {
+    if constexpr (!KDEAD) {
+        if (peel) {   // iteration 0 on the zero state
+            constexpr bool FIRST = true, DEAD = false;
+#include "ldpc5g_dec_frame_iter.h"
+        }
+    }
+    if (!active) {   // decided by the raw LLRs' syndrome
+    } else if constexpr (KDEAD) {
+        constexpr bool FIRST = false;
         constexpr uint64_t all = (1ull << (MB - 4)) - 1;
         if (live_x != all) {
             constexpr bool DEAD = true;
@@ -456,7 +487,7 @@ __device__ __forceinline__ void frame_body(
 #include "ldpc5g_dec_frame_iter.h"
         }
     } else {
-        constexpr bool DEAD = false;
+        constexpr bool FIRST = false, DEAD = false;
 #include "ldpc5g_dec_frame_iter.h"
     }
 

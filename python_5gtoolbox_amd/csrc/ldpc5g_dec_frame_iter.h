@@ -1,11 +1,30 @@
 // ldpc5g_dec_frame_iter.h — the decode iterations of frame_body (ldpc5g_dec_frame.h), included
-// inside it twice by a workgroup-uniform choice: with DEAD = true (the dead-extension-row
-// shortcuts, for a codeblock with a dead row) and DEAD = false.  A textual include rather than a
-// generic lambda: the lambda form spills VGPRs in the plain kernel (measured ~1 % slower).
+// inside it by workgroup-uniform choices: with DEAD = true (the dead-extension-row shortcuts, for
+// a codeblock with a dead row) and DEAD = false, both with FIRST = false; and once with
+// FIRST = true, DEAD = false: iteration 0 alone, peeled in front of the loop when the punctured
+// columns 0 and 1 are +0.0 (pc == 2).  A textual include rather than a generic lambda: the lambda
+// form spills VGPRs in the plain kernel (measured ~1 % slower).
 // No include guard on purpose; not a standalone header.
+//
+// FIRST relies on the state being zero and on LQ(0) = LQ(1) = +0.0:
+//  - r_old = +0.0 on every edge, so q = LQ - (+0.0) = LQ bit for bit (-0.0 included): no state
+//    read, select, sign application, sign-word walk or subtraction.
+//  - A row with a punctured column (every BG1 row, all BG2 rows but five) has min1 = |+0.0| at its
+//    first punctured edge, which is edge 0 (edges are in column order, `aq < min1` is strict), and
+//    min2 = min |LQ| over its other edges (0 when it holds both punctured columns).  Per core edge
+//    that leaves the parity compare, the sign collect and one v_min_f64.
+//  - Such a row sends +-mA = +-alpha * clamp(0) to every column >= 2 and, when it holds both
+//    punctured columns, +-0 to those too.  frame_body takes this path only when alpha * clamp(0)
+//    is +-0, so all those messages are +-0 and phase B drops them: a sum that starts at +0.0 never
+//    becomes -0.0 (x + (-x) rounds to +0.0), so S + (+-0) = S for every partial sum.  Columns no
+//    other row touches become LLR + (+0.0); only a row's message to its single punctured column
+//    (+-mB) enters the register sum S.  With no LDS add there is no group barrier.
+//  - The syndrome flag is its own word (never reset): without phase-B barriers a reset of flagA
+//    could overtake another wave's read of it.
 
     auto rdead = [&](int i) -> bool { return DEAD && i >= 4 && ((live_x >> (i - 4)) & 1u) == 0; };
-    for (; it < L; ++it) {
+    int* const flagI = FIRST ? flagA + 2 : flagA;
+    for (; it < (FIRST ? (L < 1 ? L : 1) : L); ++it) {
         // opaque per iteration: otherwise LICM hoists hundreds of loop-invariant addresses
         uint32_t sb = sb0, sbw = sbw0, tz = tz0;
         int sv = s;
@@ -45,23 +64,29 @@
             constexpr int hh = decltype(hc)::value, p = decltype(pc_)::value;
             if constexpr (p < kFrStr<BG>.n[hh]) {
                 constexpr int i = kFrStr<BG>.row[hh][p], k = kFrStr<BG>.k[hh][p];
-                tbs[p % kFrDT] = *(lds_u32*)(uintptr_t)(tz + (uint32_t)fr_cof<BG>(i, k) * 4u);
+                if constexpr (!(FIRST && P::COL[P::RS[i] + k] < 2))   // FIRST: LQ(0), LQ(1) known
+                    tbs[p % kFrDT] = *(lds_u32*)(uintptr_t)(tz + (uint32_t)fr_cof<BG>(i, k) * 4u);
             }
         };
         auto sload_a = [&](auto hc, auto pc_) {
             constexpr int hh = decltype(hc)::value, p = decltype(pc_)::value;
             if constexpr (p < kFrStr<BG>.n[hh]) {
                 constexpr int i = kFrStr<BG>.row[hh][p], k = kFrStr<BG>.k[hh][p];
-                abq[p % kFrDA] = at((uint32_t)(P::COL[P::RS[i] + k] * kFrColB) + tbs[p % kFrDT]);
+                if constexpr (!(FIRST && P::COL[P::RS[i] + k] < 2))
+                    abq[p % kFrDA] = at((uint32_t)(P::COL[P::RS[i] + k] * kFrColB) + tbs[p % kFrDT]);
             }
         };
-        // core edge k of row i: its LQ entry, and the stream moved on by one
-        auto snext = [&](auto ic, auto kc) -> T {
+        // core edge k of row i: the stream moved on by one; its LQ entry first
+        auto sskip = [&](auto ic, auto kc) {
             constexpr int i = decltype(ic)::value, k = decltype(kc)::value;
             constexpr int hh = kFrPlan<BG>.owner[i], p = kFrStr<BG>.start[i] + k;
-            const T a = abq[p % kFrDA];
             sload_a(std::integral_constant<int, hh>{}, std::integral_constant<int, p + kFrDA>{});
             sload_t(std::integral_constant<int, hh>{}, std::integral_constant<int, p + kFrDT>{});
+        };
+        auto snext = [&](auto ic, auto kc) -> T {
+            constexpr int i = decltype(ic)::value, k = decltype(kc)::value;
+            const T a = abq[(kFrStr<BG>.start[i] + k) % kFrDA];
+            sskip(ic, kc);
             return a;
         };
         auto rowA = [&](auto ic) {
@@ -134,6 +159,67 @@
             }
             put_state(ic, T(0), alpha * x2, sx >> 31, (uint32_t)(d - 1));
         };
+        // FIRST: the two row forms of the zero state (see the top).  LQ of edge k: a core entry
+        // from the stream, or LLR + r_old = LLR + (+0.0) of the extension column (-0.0 -> +0.0)
+        auto edge0 = [&](auto ic, auto kc) -> T {
+            constexpr int i = decltype(ic)::value, k = decltype(kc)::value;
+            if constexpr (P::COL[P::RS[i] + k] < KC) {
+                return snext(ic, kc);
+            } else {
+                constexpr int hh = kFrPlan<BG>.owner[i], p = kFrPlan<BG>.xpos[i];
+                const T a = xr[p % XP] + T(0);
+                xload(std::integral_constant<int, hh>{}, std::integral_constant<int, p + XP>{});
+                hdx |= (uint64_t)(a < T(0)) << (i - 4);
+                return a;
+            }
+        };
+        // the row's new state from its minima x1 <= x2: alpha * max(x - beta, 0) (:201), the signs
+        auto put_first = [&](auto ic, bool par, T x1, T x2, uint32_t negs, uint32_t idx) {
+            constexpr int d = kFrPlan<BG>.deg(decltype(ic)::value);
+            fail |= par;
+            if constexpr (OFS) {
+                x1 = x1 - beta, x2 = x2 - beta;
+                x1 = x1 > T(0) ? x1 : T(0), x2 = x2 > T(0) ? x2 : T(0);
+            }
+            const uint32_t sgn = 0u - (__builtin_popcount(negs) & 1u);
+            put_state(ic, alpha * x1, alpha * x2, negs ^ (sgn & ((1u << d) - 1u)), idx);
+        };
+        auto rowA_punct = [&](auto ic) {   // a row with a punctured column: min1 = 0 at edge 0
+            constexpr int i = decltype(ic)::value, e0 = P::RS[i], d = kFrPlan<BG>.deg(i);
+            constexpr int npun = (kFrPlan<BG>.kc[0][i] >= 0) + (kFrPlan<BG>.kc[1][i] >= 0);
+            T mn = npun > 1 ? T(0) : FT<T>::inf();   // min2: the second punctured edge is |+0.0|
+            uint32_t negs = 0;   // the punctured edges come first and shift in zeros
+            bool par = false;
+            sfor<0, d>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                if constexpr (P::COL[e0 + k] < 2) {
+                    static_assert(k < npun, "punctured edges first");
+                    sskip(ic, kc);
+                } else {
+                    const T a = edge0(ic, kc);
+                    par ^= a < T(0);
+                    negs = __builtin_amdgcn_alignbit(negs, FT<T>::sbits(a), 31);
+                    if constexpr (npun == 1) mn = fmin(mn, fabs(a));
+                }
+            });
+            put_first(ic, par, T(0), mn, negs, 0u);
+        };
+        auto rowA_zero = [&](auto ic) {   // any row on the zero state: rowA with r_old = +0.0
+            constexpr int i = decltype(ic)::value, d = kFrPlan<BG>.deg(i);
+            T min1 = FT<T>::inf(), min2 = FT<T>::inf();
+            uint32_t idx = 0, negs = 0;
+            bool par = false;
+            sfor<0, d>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                const T a = edge0(ic, kc);
+                par ^= a < T(0);
+                const T aq = fabs(a);
+                idx = aq < min1 ? (uint32_t)k : idx;
+                negs = __builtin_amdgcn_alignbit(negs, FT<T>::sbits(a), 31);
+                two_min(min1, min2, aq);
+            });
+            put_first(ic, par, min1, min2, negs, idx);
+        };
         if (active) {
             per_half([&](auto hc) {
                 sfor<0, XP>([&](auto pc_) { xload(hc, pc_); });
@@ -143,7 +229,10 @@
             sfor<0, MB>([&](auto ic) {   // one branch per row: bounded live ranges
                 constexpr int i = decltype(ic)::value;
                 if (h == kFrPlan<BG>.owner[i]) {
-                    if constexpr (DEAD && i >= 4) {
+                    if constexpr (FIRST) {
+                        if constexpr (fr_punct<BG>(i)) rowA_punct(ic);
+                        else rowA_zero(ic);
+                    } else if constexpr (DEAD && i >= 4) {
                         if (rdead(i)) rowA_dead(ic);
                         else rowA(ic);
                     } else {
@@ -151,11 +240,11 @@
                     }
                 }
             });
-            if (fail) *flagA = 1;
+            if (fail) *flagI = 1;
         }
         lds_barrier();
         // ---- the syndrome of LQ_old decides (:107-114): output its hard decisions
-        if (active && *flagA == 0) {
+        if (active && *flagI == 0) {
             hdx_keep = hdx;   // the LQ image stays frozen (no phase B) for the decisions
             if (t == 0) status[out] = 1, iters[out] = it;
             active = false;
@@ -170,7 +259,8 @@
         auto add_to = [&](auto ic, auto kc, T r, uint32_t ent) {   // column of edge k of row i
             constexpr int i = decltype(ic)::value, k = decltype(kc)::value, j = P::COL[P::RS[i] + k];
             lds_T& acc = at((uint32_t)(j * kFrColB) + ent);
-            if constexpr (kFrPlan<BG>.first_row[j] == i) acc = T(0) + r;
+            // FIRST: only the rows without a punctured column add
+            if constexpr ((FIRST ? fr_first_free<BG>(j) : kFrPlan<BG>.first_row[j]) == i) acc = T(0) + r;
             else __hip_atomic_fetch_add(&acc, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         };
         T S = T(0);
@@ -182,6 +272,59 @@
                 const int j = jcol(jj);
                 lf[jj] = ldg(lrow, (j < pc ? 0 : j - pc) * Z + sv);
             }
+        }
+        if constexpr (FIRST) {
+            // rows in order: a row with one punctured column H gives S its message (+-mB); a row
+            // with both sends only +-0; a row with none adds as in the general code, then a barrier
+            // (its columns may meet the next such row's)
+            sfor<0, MB>([&](auto ic) {
+                constexpr int i = decltype(ic)::value, e0 = P::RS[i], d = kFrPlan<BG>.deg(i);
+                if constexpr (!fr_punct<BG>(i)) {
+                    static_assert(!kFrPlan<BG>.lds[i], "a row without a punctured column is a VGPR row");
+                    if (active && h == kFrPlan<BG>.owner[i]) {
+                        T a, b;
+                        uint32_t u, idx;
+                        get_state(ic, a, b, u, idx);
+                        sfor<0, d>([&](auto kc) {
+                            constexpr int k = decltype(kc)::value, j = P::COL[e0 + k];
+                            if constexpr (j < KC) add_to(ic, kc, msg(a, b, u, idx, kc), rot(fr_cof<BG>(i, k)));
+                        });
+                    }
+                    lds_barrier();
+                } else if constexpr (!kFrPlan<BG>.both(i)) {
+                    if (active) {
+                        per_half([&](auto hc) {
+                            constexpr int H = decltype(hc)::value;
+                            if constexpr (kFrPlan<BG>.kc[H][i] >= 0) {
+                                T a, b;
+                                uint32_t u, idx;
+                                if constexpr (kFrPlan<BG>.lds[i]) {
+                                    lds_get(ic, rot((Z - fr_pf<BG>(i, H)) % Z), a, b, u, idx);
+                                } else {
+                                    static_assert(kFrPlan<BG>.owner[i] == H && kFrPlan<BG>.fr[i] == H, "own frame");
+                                    get_state(ic, a, b, u, idx);
+                                }
+                                S = S + msg(a, b, u, idx, std::integral_constant<int, kFrPlan<BG>.kc[H][i]>{});
+                            }
+                        });
+                    }
+                }
+            });
+            // ---- LQ = LLRin + sum (:126): a column no row added into holds LLR + (+0.0)
+            if (active) {
+                per_half([&](auto hc) {
+                    constexpr int H = decltype(hc)::value;
+                    sfor<0, KH>([&](auto jc) {
+                        constexpr int jj = decltype(jc)::value, j = jj == 0 ? H : jj + 1 + H * (KH - 1);
+                        lds_T& x = at((uint32_t)(j * kFrColB) + sb);
+                        if constexpr (jj == 0) x = T(0) + S;   // punctured columns: LLR 0 (:43)
+                        else if constexpr (fr_first_free<BG>(j) >= 0) x = lf[jj] + x;
+                        else x = lf[jj] + T(0);
+                    });
+                });
+            }
+        }
+        if (!FIRST && active) {
             // hand-offs: the other column's message of this half's rows with both columns
             per_half([&](auto hc) {
                 constexpr int H = decltype(hc)::value;
@@ -199,7 +342,7 @@
                 });
             });
         }
-        sfor<0, kFrPlan<BG>.ng>([&](auto gc) {
+        sfor<0, FIRST ? 0 : kFrPlan<BG>.ng>([&](auto gc) {
             constexpr int g = decltype(gc)::value;
             constexpr uint64_t gx = fr_group_xmask<BG>(g);
             const bool gdead = DEAD && gx != 0 && (live_x & gx) == 0;   // adds nothing: no barrier
@@ -249,7 +392,7 @@
             if (!gdead) lds_barrier();
         });
         // ---- LQ = LLRin + sum (:126) for the own entries
-        if (active) {
+        if (!FIRST && active) {
 #pragma unroll
             for (int jj = 0; jj < KH; ++jj) {
                 const int j = jcol(jj);
@@ -257,6 +400,6 @@
                 x = (j < pc ? T(0) : lf[jj]) + (jj == 0 ? S : x);   // punctured columns: LLR 0 (:43)
             }
         }
-        if (t == 0) *flagA = 0;   // read before the phase-B barriers
+        if (!FIRST && t == 0) *flagA = 0;   // read before the phase-B barriers
         if (!block_any(active)) break;
     }
