@@ -381,6 +381,59 @@ int ldpc5g_sch_rx_decode(const void* sym, int32_t sym_dtype, int64_t ldsym, cons
                          int8_t* tbblk, int64_t ldb, uint8_t* cb_crc_ok, uint32_t* tb_rem,
                          uint8_t* tb_ok, void* stream);
 
+/* ================================================ linear MIMO equalisation (before the chain)
+ * The producer of the `sym` / `noise_var` arguments above: the four linear algorithms of
+ * channel_equ_and_demod (py5gphy/channel_equalization/nr_channel_eq.py:12-50), which the
+ * reference calls once per resource element (RE) from the double loop of Pdsch.RX_process
+ * (nr_pdsch.py:245-263) and its PUSCH twin (nr_pusch.py:147-165), batched over the data REs of T
+ * transport blocks in one launch, one thread per RE. */
+#define LDPC5G_EQ_ZF 0        /* ZF.py:47-79   */
+#define LDPC5G_EQ_ZF_IRC 1    /* ZF.py:5-45    */
+#define LDPC5G_EQ_MMSE 2      /* MMSE.py:58-103 */
+#define LDPC5G_EQ_MMSE_IRC 3  /* MMSE.py:5-56  */
+/* Layout, per transport block t (row strides ld* in COMPLEX elements):
+ *   y   [t][r][Nr]                    received vector of RE r
+ *   h   [t][r][Nr][NL]                channel estimate of RE r
+ *   cov [t][r / re_per_cov][Nr][Nr]   noise-interference covariance of the block of RE r
+ * r = 0..R-1 is the flat RE index m*RE_num + re of the reference's loops; re_per_cov = 12
+ * reproduces its prb = re // 12 (RE_num is a multiple of 12).  re_idx: nre ascending flat indices
+ * of the data REs (the pdsch_RE_usage == 0 positions), shared by the T blocks, or NULL for all R
+ * (then nre must equal R).  An index outside 0..R-1 reads nothing and yields NaN outputs.
+ * in_dtype LDPC5G_F64: complex128 in, complex128 symbols out; LDPC5G_F32: complex64 storage in
+ * and out.  The arithmetic is float64 in both cases (the kernel is memory-bound, and a float32
+ * inversion loses the result at the condition numbers MIMO channels reach): the complex64 result
+ * is, bit for bit, the complex128 result on the widened inputs rounded to complex64.  Noise
+ * variances are always float32, as nr_Demodulation.py:24 casts them.
+ * Output: sym[t][i*NL + l] and noise_var[t][i*NL + l] for data RE i and layer l — the
+ * de-layer-mapped order in which RX_process concatenates its LLRs, i.e. the sym / noise_var of
+ * ldpc5g_demod_descramble, ldpc5g_sch_demod_raterecover and ldpc5g_sch_rx_decode with
+ * nsym = nre*NL.
+ * Supported: Nr in {1, 2, 4}, 1 <= NL <= Nr.  Anything else, a bad algo / in_dtype /
+ * re_per_cov (< 1), a row stride shorter than its row (ldy < R*Nr, ldh < R*Nr*NL,
+ * ldcov < ceil(R/re_per_cov)*Nr*Nr, ldsym or ldnv < nre*NL), nre > R, T, R or nre <= 0, or a null
+ * buffer returns LDPC5G_ESIZE; all of it is checked on the host before any HIP call.
+ * Formulas and operation order follow the reference: the Nr == 1 shortcut s = Y/H,
+ * noise_var = Re(cov / (conj(H) H)) for all four algorithms (H == 0 gives inf / NaN where the
+ * reference asserts); sigma_2 = mean of cov's diagonal; comp = 1 - diag(inv_W1), s = s_hat/comp,
+ * noise_var = 1/comp - 1 for the two MMSE forms; diag(W cov W^H) for ZF-IRC.
+ * cov and W1 (H^H H, H^H H / sigma_2 + I, H^H cov^-1 H + I) are Hermitian positive semidefinite,
+ * and the kernel relies on it: of cov it reads only the lower triangle (row >= column) and the
+ * real part of the diagonal (ZF and MMSE read the diagonal alone).
+ * Regularisation.  The reference adds 0.0012 * max|A| * I to A (W1 and, in MMSE-IRC, cov) when
+ * np.linalg.matrix_rank(A) < n, an SVD test with threshold n*eps*sigma_max whose outcome on nearly
+ * singular input is rounding noise even in numpy.  Here A is factored by unpivoted LDL^H and is
+ * regularised, then factored again, iff NOT(min_k d_k > 2^-40 * max_ij |A_ij|); the negated form
+ * also catches NaN and negative pivots.  For positive semidefinite A every pivot is >= lambda_min
+ * and max|A_ij| <= lambda_max, so the rule never fires when sigma_min/sigma_max >= 1e-8 and always
+ * fires on exactly singular input, whose last pivot is at rounding level.  Between 2^-40 (9.1e-13)
+ * and numpy's ~1e-15 the two tests may disagree; there the reference's own result has fewer than
+ * three significant digits.  Asynchronous on `stream`. */
+int ldpc5g_equalize(const void* y, int64_t ldy, const void* h, int64_t ldh,
+                    const void* cov, int64_t ldcov, int32_t in_dtype,
+                    const int32_t* re_idx, int64_t R, int64_t nre, int32_t re_per_cov,
+                    int32_t T, int32_t Nr, int32_t NL, int32_t algo,
+                    void* sym, int64_t ldsym, float* noise_var, int64_t ldnv, void* stream);
+
 /* ================================================ gather records (multi-GPU)
  * Record r (a row of rec, stride ldr bytes) = the nbits int8 bits of row r of `bits` (values 0/1)
  * packed in np.packbits order (bit i -> byte i/8, bit 7 - i%8, tail zero-padded), then

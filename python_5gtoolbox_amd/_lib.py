@@ -19,6 +19,7 @@ LLR_FULL = 1
 RATE_MATCHED = 2   # LDPC5G_RATE_MATCHED: rate-recovered rows, untransmitted columns +0.0
 ALGO_MS, ALGO_BP, ALGO_BF = 0, 1, 2
 EBGN, EZC, ESIZE, EHIP = -1, -2, -3, -4
+EQ_ALGO = {"ZF": 0, "ZF-IRC": 1, "MMSE": 2, "MMSE-IRC": 3}   # LDPC5G_EQ_*: nr_channel_eq.py:15-26
 
 # every symbol include/ldpc5g.h declares: name -> (restype, argtypes)
 _c = ctypes
@@ -121,6 +122,10 @@ SIGNATURES = {
                                            _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
                                            _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int32,
                                            _c.c_int64, _c.c_void_p]),
+    "ldpc5g_equalize": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                   _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64,
+                                   _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                   _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "ldpc5g_pack_records": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                        _c.c_void_p]),

@@ -5,6 +5,8 @@ entry points ldpc5g_prbs, ldpc5g_scramble_modulate, ldpc5g_demod_descramble (inc
     scramble_modulate(bits (T, G), mod, cinit=None) -> (T, G/Qm) complex64      (nr_pdsch_process.py:17-25)
     demod_descramble(sym (T, n), noise_var (T, n), mod, cinit=None) -> (T, n*Qm) float32 LLR
                                                       (nr_Demodulation.py:12-46, nr_pdsch.py:268-274)
+    equalize(y (T, R, Nr), h (T, R, Nr, NL), cov (T, R/12, Nr, Nr), algo, re_idx=None)
+        -> (sym (T, nre*NL), noise_var (T, nre*NL) float32)   (nr_channel_eq.py:12-26, ZF.py, MMSE.py)
 mod: a MOD_ID value (the order Qm for QPSK..1024QAM, 1 BPSK, -1 pi/2-BPSK).
 Device tensors in and out; asynchronous on the current stream.
 """
@@ -48,6 +50,47 @@ def scramble_modulate(bits, mod, cinit=None, words=None, out=None):
             w.stride(0) if w is not None else 0, T, G, int(mod), _lib.ptr(sym), sym.stride(0),
             _lib.stream_ptr(bits.device)))
     return sym
+
+
+def equalize(y, h, cov, algo, re_idx=None, re_per_cov=12, out=None):
+    """Linear MIMO equalisation of the data resource elements of T transport blocks
+    (ldpc5g_equalize; ZF.py / MMSE.py through nr_channel_eq.py:12-26).  y: (T, R, Nr), h:
+    (T, R, Nr, NL), cov: (T, ceil(R/re_per_cov), Nr, Nr) complex64 / complex128 device tensors of
+    one dtype (rows may be padded: only stride(0) is free); algo: "ZF", "ZF-IRC", "MMSE" or
+    "MMSE-IRC"; re_idx: (nre,) int32 ascending flat indices of the data REs, None for all R.
+    Returns (sym (T, nre*NL) of the input dtype, noise_var (T, nre*NL) float32), or fills
+    out=(sym, noise_var)."""
+    t = _lib.require_gpu()
+    assert algo in _lib.EQ_ALGO, f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO)}"
+    assert y.dim() == 3 and h.dim() == 4 and cov.dim() == 4
+    assert y.dtype in (t.complex64, t.complex128) and h.dtype == y.dtype and cov.dtype == y.dtype
+    T, R, Nr = y.shape
+    NL = h.shape[3]
+    ncov = (R + int(re_per_cov) - 1) // int(re_per_cov) if re_per_cov >= 1 else 0
+    assert h.shape == (T, R, Nr, NL) and cov.shape[0] == T and cov.shape[1] >= ncov and cov.shape[2:] == (Nr, Nr)
+    assert y[0].is_contiguous() and h[0].is_contiguous() and cov[0].is_contiguous(), \
+        "only the transport-block stride is free"
+    if re_idx is not None:
+        assert re_idx.dim() == 1 and re_idx.dtype == t.int32 and re_idx.is_contiguous()
+        assert re_idx.device == y.device
+    nre = re_idx.shape[0] if re_idx is not None else R
+    if out is not None:
+        sym, nv = out
+        assert sym.dtype == y.dtype and sym.shape == (T, nre * NL) and sym.stride(1) == 1
+        assert nv.dtype == t.float32 and nv.shape == (T, nre * NL) and nv.stride(1) == 1
+    else:
+        sym = t.empty((T, nre * NL), dtype=y.dtype, device=y.device)
+        nv = t.empty((T, nre * NL), dtype=t.float32, device=y.device)
+    def ld(x, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
+        return x.stride(0) if T > 1 else row
+    with t.cuda.device(y.device):
+        _lib.check(_lib.lib().ldpc5g_equalize(
+            _lib.ptr(y), ld(y, R * Nr), _lib.ptr(h), ld(h, R * Nr * NL), _lib.ptr(cov),
+            ld(cov, cov.shape[1] * Nr * Nr), _lib.F32 if y.dtype == t.complex64 else _lib.F64,
+            _lib.ptr(re_idx) if re_idx is not None else None, R, nre, int(re_per_cov), T, Nr, NL,
+            _lib.EQ_ALGO[algo], _lib.ptr(sym), ld(sym, nre * NL), _lib.ptr(nv), ld(nv, nre * NL),
+            _lib.stream_ptr(y.device)))
+    return sym, nv
 
 
 def demod_descramble(sym, noise_var, mod, cinit=None, words=None, out=None, llr_dtype=None):

@@ -7,6 +7,8 @@ one configuration — the C-ABI entry points ldpc5g_sch_* of include/ldpc5g.h.
     sch_decode_batch(llr[T, E_total], cfg, L, ...) -> SchDecodeResult      (nr_dlsch_decode.py)
     sch_demod_raterecover_batch(sym[T, E_total/Qm], noise_var, mod, cfg, ...) -> llr_dn[T*C, N]
     sch_rx_batch(sym, noise_var, mod, cfg, L, ...) -> SchDecodeResult      (nr_pdsch.py:245-281)
+    sch_eq_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, ...) -> SchDecodeResult   (the same, from
+        the received resource grid, channel estimate and covariance: phy.equalize first)
 
 Device tensors in, device tensors out, everything asynchronous on the current stream; torch only
 allocates the buffers.  The per-transport-block drop-ins (nr_dlsch.DLSCHEncode,
@@ -347,6 +349,21 @@ def sch_rx_batch(sym, noise_var, mod, cfg, L, algo="min-sum", alpha=1.0, beta=0.
         sch_tb_check_batch(ws.dec_ck, cfg, T, ws)
     return SchDecodeResult(ws.tb_ok, ws.tbblk, llr_dn, ws.dec_ck, ws.status, ws.iters, ws.cb_ok,
                            ws.tb_rem)
+
+
+def sch_eq_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, re_per_cov=12, **kw):
+    """The body of the reference's RX_process from (pdsch_resource, H_result, cov_m) to the
+    transport block (nr_pdsch.py:245-281): phy.equalize (ZF / ZF-IRC / MMSE / MMSE-IRC per data
+    resource element) followed by sch_rx_batch, whose keyword arguments all pass through.  y, h,
+    cov, algo, re_idx, re_per_cov as phy.equalize; mod, cfg, L as sch_rx_batch.  The data REs must
+    carry exactly the transport block: nre * NL * Qm == cfg.G."""
+    from . import phy
+    nre = re_idx.shape[0] if re_idx is not None else y.shape[1]
+    NL = h.shape[3]
+    assert nre * NL * phy.bits_per_symbol(mod) == cfg.G, \
+        f"nre*NL*Qm = {nre}*{NL}*{phy.bits_per_symbol(mod)} != G = {cfg.G}"
+    sym, nv = phy.equalize(y, h, cov, algo, re_idx, re_per_cov)
+    return sch_rx_batch(sym, nv, mod, cfg, L, **kw)
 
 
 # ------------------------------------------------------------ per-TB configurations (multi)
