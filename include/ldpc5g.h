@@ -434,6 +434,55 @@ int ldpc5g_equalize(const void* y, int64_t ldy, const void* h, int64_t ldh,
                     int32_t T, int32_t Nr, int32_t NL, int32_t algo,
                     void* sym, int64_t ldsym, float* noise_var, int64_t ldnv, void* stream);
 
+/* ================================================ maximum-likelihood MIMO detection
+ * The second producer of the receive chain: the ML family of channel_equ_and_demod
+ * (nr_channel_eq.py:27-46) emits LLRs directly, so its output feeds ldpc5g_sch_decode and bypasses
+ * ldpc5g_demod_descramble.  Batched over the data REs of T transport blocks in one launch. */
+#define LDPC5G_ML_SOFT 0       /* ML.py:47-98 "soft"; irc: ML.py:9-45.  LLRs by ML_soft_LLR_est, :100-139 */
+#define LDPC5G_ML_HARD 1       /* ML.py:47-98 "hard": LLR = 1 - 2 bit (:93-94)                          */
+#define LDPC5G_ML2_SOFT 2      /* ML2.py:47-161; irc: ML2.py:9-45.  LLR = min1 - min0 per bit (:138-160) */
+#define LDPC5G_ML_MMSE 3       /* MMSE_ML.py:47-105 (subset_ML :71-105); irc: MMSE_ML.py:12-45          */
+#define LDPC5G_ML_OPT_RANK2 4  /* opt_rank2_ML.py:38-171; irc: :9-36.  NL != 2 runs LDPC5G_ML_SOFT (:44) */
+/* y, h, cov, in_dtype, re_idx, R, nre, re_per_cov, T, Nr, NL: exactly as ldpc5g_equalize (layouts,
+ * the cov triangle that is read, NaN outputs for an index outside 0..R-1).  mod: the modulation id
+ * used elsewhere; pi/2-BPSK (-1) detects as BPSK, because the reference's get_mod_list and
+ * get_oppisite_syms only ever modulate symbol index 0.  irc: 0, or 1 for the -IRC form of `algo`.
+ * The arithmetic is float64 for both storage types; the complex64 run is bit-equal to the
+ * complex128 run on the widened inputs.
+ * Per RE.  Without irc sigma^2 = Re(mean(diag(cov))).  With irc Y and H are whitened by
+ * U = D^-1/2 L^-1 of the unpivoted LDL^H factorisation of cov (U^H U = cov^-1; the metric does not
+ * depend on the choice of U, the reference's cov_inverse_decompose takes one from eigh) and
+ * sigma^2 = 1; cov is first regularised (+ 0.0012 max|cov| I) by the pivot rule described under
+ * ldpc5g_equalize, which stands in for cov_inverse_decompose's matrix_rank loop.  The metric is
+ * v(S) = |Y - H S|^2 / sigma^2 over the reference's constellation (get_mod_list: float32 mapper
+ * values widened; point m has the binary digits of m, MSB first, as bits).
+ *   ML-soft, ML-hard, ML2-soft: all M^NL candidates in itertools.product order (layer 0 slowest);
+ *     ties go to the LOWEST candidate index (the reference's strict `<`).  Cap: M^NL <= 65536, i.e.
+ *     NL*Qm <= 16 (QPSK / 16QAM to NL = 4, 64QAM / 256QAM to NL = 2, 1024QAM at NL = 1).
+ *   MMSE-ML: the MMSE (irc: MMSE-IRC) estimate of ldpc5g_equalize, then per layer its min(4, M)
+ *     nearest points, and the search over their <= 256 combinations; no cap.
+ *   opt-rank2-ML at NL = 2: the reference's O(M) loop over s0 with the per-axis choice of s1; no
+ *     cap (the only search for 1024QAM on two layers).  The reference repeats the loop with the
+ *     layers swapped and asserts that both agree; the result is the first loop's.
+ * Outputs, for data RE i, layer l, bit m (positive LLR means bit 0):
+ *   llr[t][(i*NL + l)*Qm + m], float64 (llr_dtype LDPC5G_F64, the reference's type) or float32
+ *     (the float64 value rounded once); multiplied by 1 - 2 c(n) when prbs (ldpc5g_prbs words,
+ *     row stride ldw) is given, as ldpc5g_demod_descramble does;
+ *   sym[t][i*NL + l] complex64 or NULL: the decided point (min_S is 'c8' in the reference);
+ *   noise_var[t][i*NL + l] or NULL, in llr_dtype: the minimum metric (the same for every layer);
+ *   hardbits[t][(i*NL + l)*Qm + m] int8 or NULL: the decided bits.
+ * Every unsupported combination (Nr, NL, mod, algo, irc, dtypes, re_per_cov < 1, NL*Qm over the
+ * cap — that message names opt-rank2-ML), a row stride shorter than its row, bad sizes or a null
+ * required buffer returns LDPC5G_ESIZE with a message; all of it is checked on the host before
+ * any HIP call.  Asynchronous on `stream`. */
+int ldpc5g_ml_detect(const void* y, int64_t ldy, const void* h, int64_t ldh,
+                     const void* cov, int64_t ldcov, int32_t in_dtype,
+                     const int32_t* re_idx, int64_t R, int64_t nre, int32_t re_per_cov,
+                     int32_t T, int32_t Nr, int32_t NL, int32_t mod, int32_t algo, int32_t irc,
+                     const uint32_t* prbs, int64_t ldw, void* llr, int32_t llr_dtype, int64_t ldllr,
+                     void* sym, int64_t ldsym, void* noise_var, int64_t ldnv,
+                     int8_t* hardbits, int64_t ldhb, void* stream);
+
 /* ================================================ gather records (multi-GPU)
  * Record r (a row of rec, stride ldr bytes) = the nbits int8 bits of row r of `bits` (values 0/1)
  * packed in np.packbits order (bit i -> byte i/8, bit 7 - i%8, tail zero-padded), then

@@ -20,6 +20,10 @@ RATE_MATCHED = 2   # LDPC5G_RATE_MATCHED: rate-recovered rows, untransmitted col
 ALGO_MS, ALGO_BP, ALGO_BF = 0, 1, 2
 EBGN, EZC, ESIZE, EHIP = -1, -2, -3, -4
 EQ_ALGO = {"ZF": 0, "ZF-IRC": 1, "MMSE": 2, "MMSE-IRC": 3}   # LDPC5G_EQ_*: nr_channel_eq.py:15-26
+# nr_channel_eq.py:27-46 names -> (LDPC5G_ML_* algo, irc)
+ML_ALGO = {"ML-soft": (0, 0), "ML-IRC-soft": (0, 1), "ML-hard": (1, 0), "ML-IRC-hard": (1, 1),
+           "ML2-soft": (2, 0), "ML2-IRC-soft": (2, 1), "MMSE-ML": (3, 0), "MMSE-ML-IRC": (3, 1),
+           "opt-rank2-ML": (4, 0), "opt-rank2-ML-IRC": (4, 1)}
 
 # every symbol include/ldpc5g.h declares: name -> (restype, argtypes)
 _c = ctypes
@@ -126,6 +130,12 @@ SIGNATURES = {
                                    _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64,
                                    _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
                                    _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "ldpc5g_ml_detect": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                    _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64,
+                                    _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                    _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                    _c.c_int32, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                    _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "ldpc5g_pack_records": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                        _c.c_void_p]),

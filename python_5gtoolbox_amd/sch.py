@@ -9,6 +9,8 @@ one configuration — the C-ABI entry points ldpc5g_sch_* of include/ldpc5g.h.
     sch_rx_batch(sym, noise_var, mod, cfg, L, ...) -> SchDecodeResult      (nr_pdsch.py:245-281)
     sch_eq_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, ...) -> SchDecodeResult   (the same, from
         the received resource grid, channel estimate and covariance: phy.equalize first)
+    sch_ml_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, ...) -> SchDecodeResult   (the same with a
+        maximum-likelihood detector: phy.ml_detect, whose LLRs go straight to sch_decode_batch)
 
 Device tensors in, device tensors out, everything asynchronous on the current stream; torch only
 allocates the buffers.  The per-transport-block drop-ins (nr_dlsch.DLSCHEncode,
@@ -364,6 +366,26 @@ def sch_eq_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, re_per_cov=12, **kw):
         f"nre*NL*Qm = {nre}*{NL}*{phy.bits_per_symbol(mod)} != G = {cfg.G}"
     sym, nv = phy.equalize(y, h, cov, algo, re_idx, re_per_cov)
     return sch_rx_batch(sym, nv, mod, cfg, L, **kw)
+
+
+def sch_ml_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, re_per_cov=12, cinit=None, **kw):
+    """sch_eq_rx_batch for the maximum-likelihood detectors of channel_equ_and_demod
+    (nr_channel_eq.py:27-46), which emit LLRs themselves: phy.ml_detect (descrambling with cinit
+    fused) followed by sch_decode_batch, whose keyword arguments all pass through (its `algo` is
+    given as dec_algo=).  y, h, cov, algo, re_idx, re_per_cov as phy.ml_detect; mod, cfg, L as
+    sch_decode_batch.  The LLRs are float32 for schedule="layered" and float64 otherwise.  The
+    data REs must carry exactly the transport block: nre * NL * Qm == cfg.G."""
+    from . import phy
+    t = _lib.require_gpu()
+    nre = re_idx.shape[0] if re_idx is not None else y.shape[1]
+    NL = h.shape[3]
+    assert nre * NL * phy.bits_per_symbol(mod) == cfg.G, \
+        f"nre*NL*Qm = {nre}*{NL}*{phy.bits_per_symbol(mod)} != G = {cfg.G}"
+    if "dec_algo" in kw:
+        kw["algo"] = kw.pop("dec_algo")
+    llr_dtype = t.float32 if kw.get("schedule") == "layered" else t.float64
+    llr = phy.ml_detect(y, h, cov, mod, algo, re_idx, re_per_cov, cinit=cinit, llr_dtype=llr_dtype)
+    return sch_decode_batch(llr, cfg, L, **kw)
 
 
 # ------------------------------------------------------------ per-TB configurations (multi)
