@@ -483,6 +483,99 @@ int ldpc5g_ml_detect(const void* y, int64_t ldy, const void* h, int64_t ldh,
                      void* sym, int64_t ldsym, void* noise_var, int64_t ldnv,
                      int8_t* hardbits, int64_t ldhb, void* stream);
 
+/* ================================================ DMRS channel estimation (before the detectors)
+ * The producer of the `h` and `cov` arguments of ldpc5g_equalize / ldpc5g_ml_detect: the four
+ * CE_algo values of NrChannelEstimation.channel_est (py5gphy/channel_estimate/
+ * nr_channel_estimation.py:116-126), batched over T slots, with the noise-plus-interference
+ * covariance and the timing-offset estimate and compensation.  Frequency-offset estimation and
+ * compensation (nr_channel_estimation.py:224-327) and the CubicSpline / PchipInterpolator
+ * frequency interpolators (dft_dct_CE.py:147-152) are not provided. */
+#define LDPC5G_CE_DFT 0            /* dft_dct_CE.py:10-102, model "DFT"            */
+#define LDPC5G_CE_DCT 1            /* dft_dct_CE.py:10-102, model "DCT"            */
+#define LDPC5G_CE_DFT_SYMMETRIC 2  /* dft_dct_symmetric_CE.py:11-118, model "DFT" */
+#define LDPC5G_CE_DCT_SYMMETRIC 3  /* dft_dct_symmetric_CE.py:11-118, model "DCT" */
+/* Layout, per slot t (row strides ld* in COMPLEX elements):
+ *   h_ls [t][m][n][Nr][Nt]        least-squares estimate at DMRS symbol m (slot symbol sym_idx[m],
+ *                                 a HOST array of S entries), reference RE n = 0..N-1, D = RE_distance
+ *                                 subcarriers apart; PRB = N*D/12
+ *   h    [t][s*N*D + k][Nr][Nt]   H_result, s = 0..13: ldpc5g_equalize's h with R = 14*N*D
+ *   cov  [t][s*PRB + p][Nr][Nr]   cov_m: ldpc5g_equalize's cov with re_per_cov = 12
+ * in_dtype LDPC5G_F64 (complex128) or LDPC5G_F32 (complex64 storage in and out).  All arithmetic
+ * is float64 for both (the reference transforms complex64 data in single precision; its own
+ * rounding is the floor of any comparison): the complex64 result is, bit for bit, the complex128
+ * result on the widened inputs rounded to complex64.  Results are bit-identical from run to run
+ * (fixed summation order, no atomics).  At most three kernel launches, asynchronous on `stream`,
+ * no host synchronisation and no allocation: intermediates (float64 H_est, the residual, the
+ * timing offsets) live in `work`, at least ldpc5g_ce_workspace_bytes(T, S, N, Nr, Nt, D) bytes of
+ * 16-byte aligned device memory that must not be shared by calls that may run concurrently.
+ * Per sequence x = h_ls[t][m][:][nr][nt] (dft_dct_CE.py:48-94, dft_dct_symmetric_CE.py:50-110):
+ *   0 (to_comp != 0) timing offset: the (nr, nt) pair with the largest mean |x|^2 over (S, N), nt
+ *     outer, nr inner, strict > (find_peak_H_LS, nr_channel_estimation.py:66-83); TO_est[m] =
+ *     mean_n atan2(c.imag, c.real) / (2 pi D scs 1000), c = pk[m][n+1] conj(pk[m][n]) (:150-172);
+ *     every h_ls[m][n] is multiplied by exp(-j 2 pi mean(TO_est) D n scs 1000) (:174-207);
+ *   1 edge extension (HLS_extra, dft_dct_CE.py:104-133): reK = eK + (N + eK) % 2; the degree-1
+ *     least-squares line through the first 24/D points gives eK points on the left, the one
+ *     through the last 24/D points reK on the right; the symmetric algorithms append the mirrored
+ *     sequence (dft_dct_symmetric_CE.py:60-62).  M = N + eK + reK, or twice that; eK is the
+ *     caller's eRB*12 // D;
+ *   2 orthonormal inverse DFT of the ifftshift-ed sequence (dft_dct_CE.py:59) or orthonormal
+ *     DCT-II of the real and imaginary parts (:61);
+ *   3 window in samples, L_left / L_right, computed BY THE CALLER with the reference's own double
+ *     expressions, which the two files word differently (dft_dct_CE.py:64-68,
+ *     dft_dct_symmetric_CE.py:73-79);
+ *   4 P = mean |tap[L_left : M - L_right]|^2; tap k is kept iff |tap[k]| >= sqrt(P / 2) and k is
+ *     outside [L_left, M - L_right) (dft_dct_CE.py:71-80);
+ *   5 orthonormal forward DFT + fftshift, or inverse DCT, of the kept taps (:83-86);
+ *   6 linear interpolation to every subcarrier, the last value held (np.interp, :135-157); the
+ *     symmetric algorithms interpolate the full-length sequence (their H_comb is never used,
+ *     dft_dct_symmetric_CE.py:98-105);
+ *   7 crop: H_est[m][:][nr][nt] = intp[eK*D : eK*D + N*D] (:92).
+ * Per slot: 8 the degree-1 least-squares line over sym_idx per (subcarrier, nr, nt), evaluated at
+ * symbols 0..13; S = 1 copies (timing_interpolate_to_14_symbol, :159-178).  9 covariance
+ * (cov_m_estimate, :180-257): nHS = h_ls (compensated) - H_est[:, ::D]; groups of 16 PRB
+ * (16*12/D DMRS REs), a residue merged into the last full group; per DMRS symbol and group
+ * sum_re nHS[re] nHS[re]^H / count / Nt for every PRB of the group; times 2 when num_cdm_groups
+ * == 1; then the time rule of step 8.
+ * Twiddles: an on-chip table filled by one sincospi per entry of the exact rational j/M and
+ * indexed by the reduced integer (k n) mod M (DCT: k (2n+1) mod 4M) — accurate to float64 for
+ * every M; the transforms are direct sums (M is not a power of two), the forward DFT after one
+ * decimation step by the largest power of two <= 8 that divides M.
+ * Optional outputs (NULL to skip), contiguous:
+ *   h_ls_comp [t][m][n][Nr][Nt] (row stride ldhc; to_comp only; must not overlap h_ls): the
+ *             compensated h_ls, what comp_H_LS_timing_offset leaves in the caller's array
+ *   h_est     [t][m][N*D][Nr][Nt], in_dtype         noise_power [t][m][Nr][Nt] float64 (P of step 4)
+ *   taps      [t][m][Nr][Nt][M] uint8 kept mask     to_est [t][S], to_avg [t] float64 (seconds;
+ *             computed whenever either is asked for, also without to_comp, as channel_est does)
+ * Limits, all checked on the host BEFORE any HIP call (LDPC5G_ESIZE and a ldpc5g_last_error()
+ * message naming the field): Nr in {1, 2, 4} and 1 <= Nt <= Nr (the equaliser's); 1 <= S <= 4
+ * with sym_idx strictly ascending in 0..13; D in {2, 4}; N*D a multiple of 12 and PRB >= 16 (below
+ * that the reference's grouping has num_of_M_prbs = -1 and indexes out of range, :199-206: there is
+ * nothing to reproduce); M <= 2048, which covers 275 PRB at D = 4 with the symmetric extension up
+ * to eRB = 8 (2*(825 + 24 + 25) = 1748); at D = 2 the symmetric extension reaches it near 160 PRB; 0 <= L_left,
+ * L_right and L_left + L_right < M (otherwise the reference's noise mean is over an empty slice);
+ * scs in {15, 30} (nr_channel_estimation.py:60); num_cdm_groups in 1..3; a known in_dtype and
+ * algo; row strides at least their rows; T in 1..65535; a large enough workspace; non-null
+ * required buffers. */
+int64_t ldpc5g_ce_workspace_bytes(int32_t T, int32_t S, int32_t N, int32_t Nr, int32_t Nt, int32_t D);
+int ldpc5g_channel_estimate(const void* h_ls, int64_t ldhls, int32_t in_dtype, int32_t T, int32_t S,
+                            int32_t N, int32_t Nr, int32_t Nt, int32_t D, const int32_t* sym_idx,
+                            int32_t algo, int32_t eK, int32_t L_left, int32_t L_right,
+                            int32_t num_cdm_groups, int32_t to_comp, int32_t scs,
+                            void* h, int64_t ldh, void* cov, int64_t ldcov,
+                            void* work, int64_t work_bytes, void* h_ls_comp, int64_t ldhc,
+                            void* h_est, double* noise_power, uint8_t* taps, double* to_est,
+                            double* to_avg, void* stream);
+/* Timing-offset compensation of the data REs (comp_pdsch_timing_offset,
+ * nr_channel_estimation.py:209-221): out[t][m][k][r] = y[t][m][k][r] *
+ * exp(-j 2 pi to_avg[t] k scs 1000) for nsym symbols of RE resource elements (k the RE index in
+ * the allocation) and Nr antennas; to_avg: T float64 on the device (ldpc5g_channel_estimate's
+ * to_avg).  out may be y (in place).  float64 arithmetic; in_dtype as above.  Nr in 1..64, scs in
+ * {15, 30}, T in 1..65535, nsym in 1..1024, RE in 1..2^20, row strides (complex elements) at least
+ * nsym*RE*Nr, non-null buffers: anything else returns LDPC5G_ESIZE before any HIP call. */
+int ldpc5g_to_compensate(const void* y, int64_t ldy, void* out, int64_t ldo, int32_t in_dtype,
+                         const double* to_avg, int32_t T, int64_t nsym, int64_t RE, int32_t Nr,
+                         int32_t scs, void* stream);
+
 /* ================================================ gather records (multi-GPU)
  * Record r (a row of rec, stride ldr bytes) = the nbits int8 bits of row r of `bits` (values 0/1)
  * packed in np.packbits order (bit i -> byte i/8, bit 7 - i%8, tail zero-padded), then

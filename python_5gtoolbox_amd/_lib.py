@@ -24,6 +24,8 @@ EQ_ALGO = {"ZF": 0, "ZF-IRC": 1, "MMSE": 2, "MMSE-IRC": 3}   # LDPC5G_EQ_*: nr_c
 ML_ALGO = {"ML-soft": (0, 0), "ML-IRC-soft": (0, 1), "ML-hard": (1, 0), "ML-IRC-hard": (1, 1),
            "ML2-soft": (2, 0), "ML2-IRC-soft": (2, 1), "MMSE-ML": (3, 0), "MMSE-ML-IRC": (3, 1),
            "opt-rank2-ML": (4, 0), "opt-rank2-ML-IRC": (4, 1)}
+# CE_config["CE_algo"] (nr_channel_estimation.py:117-124) -> LDPC5G_CE_*
+CE_ALGO = {"DFT": 0, "DCT": 1, "DFT_symmetric": 2, "DCT_symmetric": 3}
 
 # every symbol include/ldpc5g.h declares: name -> (restype, argtypes)
 _c = ctypes
@@ -136,6 +138,19 @@ SIGNATURES = {
                                     _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                     _c.c_int32, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                     _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "ldpc5g_ce_workspace_bytes": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                               _c.c_int32, _c.c_int32]),
+    "ldpc5g_channel_estimate": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32,
+                                           _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                           _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
+                                           _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                           _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
+                                           _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
+                                           _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                           _c.c_void_p, _c.c_void_p]),
+    "ldpc5g_to_compensate": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
+                                        _c.c_void_p, _c.c_int32, _c.c_int64, _c.c_int64, _c.c_int32,
+                                        _c.c_int32, _c.c_void_p]),
     "ldpc5g_pack_records": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                        _c.c_void_p]),

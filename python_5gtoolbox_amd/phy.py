@@ -9,6 +9,10 @@ entry points ldpc5g_prbs, ldpc5g_scramble_modulate, ldpc5g_demod_descramble (inc
         -> (sym (T, nre*NL), noise_var (T, nre*NL) float32)   (nr_channel_eq.py:12-26, ZF.py, MMSE.py)
     ml_detect(y, h, cov, mod, algo, re_idx=None, ...) -> (T, nre*NL*Qm) float64 LLR [, sym, noise_var, hardbits]
                                       (nr_channel_eq.py:27-46, ML.py, ML2.py, MMSE_ML.py, opt_rank2_ML.py)
+    channel_estimate(h_ls (T, S, N, Nr, Nt), sym_map, algo, scs, eRB, l_left_ns, l_right_ns, ...)
+        -> (h (T, 14*N*D, Nr, Nt), cov (T, 14*PRB, Nr, Nr))   (dft_dct_CE.py, dft_dct_symmetric_CE.py,
+                                                              nr_channel_estimation.py:66-83,150-221)
+    to_compensate(y (T, nsym, RE, Nr), to_avg (T,), scs)       (nr_channel_estimation.py:209-221)
 mod: a MOD_ID value (the order Qm for QPSK..1024QAM, 1 BPSK, -1 pi/2-BPSK).
 Device tensors in and out; asynchronous on the current stream.
 """
@@ -146,6 +150,112 @@ def ml_detect(y, h, cov, mod, algo, re_idx=None, re_per_cov=12, cinit=None, word
             opt(outs["sym"]), nre * NL, opt(outs["noise_var"]), nre * NL, opt(outs["hardbits"]), nbits,
             _lib.stream_ptr(y.device)))
     return (llr, *(outs[k] for k in want)) if want else llr
+
+
+def ce_lengths(n, algo, eRB, re_distance=4):
+    """(eK, right_eK, M): extension points per side and the transform length of an N-point DMRS
+    sequence (dft_dct_CE.py:29,38; dft_dct_symmetric_CE.py:60)."""
+    eK = int(eRB) * 12 // int(re_distance)
+    right_eK = eK + (int(n) + eK) % 2
+    M = int(n) + eK + right_eK
+    return eK, right_eK, 2 * M if algo.endswith("_symmetric") else M
+
+
+def ce_window(algo, M, scs, re_distance, l_left_ns, l_right_ns):
+    """(L_left, L_right) in samples: the reference's own double expressions, which its two files
+    word differently (dft_dct_CE.py:64-68; dft_dct_symmetric_CE.py:73-79)."""
+    if algo.endswith("_symmetric"):
+        h_sym_sample_rate_in_hz = M * scs * 1000 * re_distance
+        L_left = int(l_left_ns / (10**9 / h_sym_sample_rate_in_hz))
+        L_left = min(M // 3 + M // 16, L_left)
+        return L_left, L_left
+    h_sym_sample_rate_in_hz = scs * 1000 * re_distance * M
+    return int(l_left_ns * 1e-9 * h_sym_sample_rate_in_hz), int(l_right_ns * 1e-9 * h_sym_sample_rate_in_hz)
+
+
+CE_WANT = ("h_est", "noise_power", "taps", "to_est", "to_avg", "h_ls_comp")
+
+
+def channel_estimate(h_ls, sym_map, algo, scs, eRB, l_left_ns, l_right_ns, re_distance=4, num_cdm_groups=2,
+                     to_comp=False, out=None, want=(), work=None):
+    """DFT / DCT channel estimation of T slots with the noise-plus-interference covariance and the
+    optional timing-offset compensation (ldpc5g_channel_estimate; dft_dct_CE.py,
+    dft_dct_symmetric_CE.py, nr_channel_estimation.py:66-83,150-221).  h_ls: (T, S, N, Nr, Nt)
+    complex64 / complex128 device tensor (only stride(0) is free); sym_map: the S DMRS symbol
+    indices (RSSymMap); algo: "DFT", "DCT", "DFT_symmetric" or "DCT_symmetric"; scs in kHz; eRB
+    extra PRBs per side; l_left_ns / l_right_ns the window lengths in ns.  Returns (h (T,
+    14*N*D, Nr, Nt), cov (T, 14*PRB, Nr, Nr)) of the input dtype — phy.equalize's and
+    phy.ml_detect's h and cov with re_per_cov = 12 — or fills out=(h, cov).  With want= (any of
+    "h_est" (T, S, N*D, Nr, Nt), "noise_power" (T, S, Nr, Nt) float64, "taps" (T, S, Nr, Nt, M)
+    uint8 kept mask, "to_est" (T, S) and "to_avg" (T,) float64 seconds, "h_ls_comp" the compensated
+    h_ls (to_comp only)) a dict of those is returned as a third value."""
+    t = _lib.require_gpu()
+    assert algo in _lib.CE_ALGO, f"algo {algo!r}: one of {sorted(_lib.CE_ALGO)}"
+    assert all(w in CE_WANT for w in want), want
+    assert h_ls.dim() == 5 and h_ls.dtype in (t.complex64, t.complex128)
+    assert h_ls[0].is_contiguous(), "only the slot stride is free"
+    T, S, N, Nr, Nt = h_ls.shape
+    D = int(re_distance)
+    sym = [int(s) for s in sym_map]
+    assert len(sym) == S, f"{len(sym)} symbol indices for S={S} DMRS symbols"
+    eK, _, M = ce_lengths(N, algo, eRB, D)
+    L_left, L_right = ce_window(algo, M, int(scs), D, l_left_ns, l_right_ns)
+    ND = N * D
+    PRB = ND // 12
+    dev = h_ls.device
+    if out is not None:
+        h, cov = out
+        assert h.dtype == h_ls.dtype and h.shape == (T, 14 * ND, Nr, Nt) and h[0].is_contiguous()
+        assert cov.dtype == h_ls.dtype and cov.shape == (T, 14 * PRB, Nr, Nr) and cov[0].is_contiguous()
+    else:
+        h = t.empty((T, 14 * ND, Nr, Nt), dtype=h_ls.dtype, device=dev)
+        cov = t.empty((T, 14 * PRB, Nr, Nr), dtype=h_ls.dtype, device=dev)
+    need = int(_lib.lib().ldpc5g_ce_workspace_bytes(T, S, N, Nr, Nt, D))
+    if work is None:
+        work = t.empty((max(need, 16),), dtype=t.uint8, device=dev)
+    assert work.dtype == t.uint8 and work.is_contiguous() and work.device == dev
+    outs = {
+        "h_est": t.empty((T, S, ND, Nr, Nt), dtype=h_ls.dtype, device=dev) if "h_est" in want else None,
+        "noise_power": t.empty((T, S, Nr, Nt), dtype=t.float64, device=dev) if "noise_power" in want else None,
+        "taps": t.empty((T, S, Nr, Nt, M), dtype=t.uint8, device=dev) if "taps" in want else None,
+        "to_est": t.empty((T, S), dtype=t.float64, device=dev) if "to_est" in want else None,
+        "to_avg": t.empty((T,), dtype=t.float64, device=dev) if "to_avg" in want else None,
+        "h_ls_comp": t.empty((T, S, N, Nr, Nt), dtype=h_ls.dtype, device=dev) if "h_ls_comp" in want else None}
+    def ld(x, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
+        return x.stride(0) if T > 1 else row
+    def opt(x):
+        return _lib.ptr(x) if x is not None else None
+    sym_arr = (_lib.ctypes.c_int32 * max(S, 1))(*sym)
+    with t.cuda.device(dev):
+        _lib.check(_lib.lib().ldpc5g_channel_estimate(
+            _lib.ptr(h_ls), ld(h_ls, S * N * Nr * Nt), _lib.F32 if h_ls.dtype == t.complex64 else _lib.F64,
+            T, S, N, Nr, Nt, D, sym_arr, _lib.CE_ALGO[algo], eK, L_left, L_right, int(num_cdm_groups),
+            1 if to_comp else 0, int(scs), _lib.ptr(h), ld(h, 14 * ND * Nr * Nt), _lib.ptr(cov),
+            ld(cov, 14 * PRB * Nr * Nr), _lib.ptr(work), work.numel(), opt(outs["h_ls_comp"]), S * N * Nr * Nt,
+            opt(outs["h_est"]), opt(outs["noise_power"]), opt(outs["taps"]), opt(outs["to_est"]),
+            opt(outs["to_avg"]), _lib.stream_ptr(dev)))
+    return (h, cov, {k: outs[k] for k in want}) if want else (h, cov)
+
+
+def to_compensate(y, to_avg, scs, out=None):
+    """Timing-offset compensation of the data REs (ldpc5g_to_compensate; comp_pdsch_timing_offset,
+    nr_channel_estimation.py:209-221): y (T, nsym, RE, Nr) complex64 / complex128 times
+    exp(-j 2 pi to_avg[t] k scs 1000), k the RE index; to_avg: (T,) float64 device tensor
+    (channel_estimate's want="to_avg").  Returns a new tensor, or fills out (which may be y)."""
+    t = _lib.require_gpu()
+    assert y.dim() == 4 and y.dtype in (t.complex64, t.complex128) and y[0].is_contiguous()
+    T, nsym, RE, Nr = y.shape
+    assert to_avg.shape == (T,) and to_avg.dtype == t.float64 and to_avg.is_contiguous() and to_avg.device == y.device
+    if out is None:
+        out = t.empty((T, nsym, RE, Nr), dtype=y.dtype, device=y.device)
+    assert out.dtype == y.dtype and out.shape == y.shape and out[0].is_contiguous()
+    row = nsym * RE * Nr
+    with t.cuda.device(y.device):
+        _lib.check(_lib.lib().ldpc5g_to_compensate(
+            _lib.ptr(y), y.stride(0) if T > 1 else row, _lib.ptr(out), out.stride(0) if T > 1 else row,
+            _lib.F32 if y.dtype == t.complex64 else _lib.F64, _lib.ptr(to_avg), T, nsym, RE, Nr, int(scs),
+            _lib.stream_ptr(y.device)))
+    return out
 
 
 def demod_descramble(sym, noise_var, mod, cinit=None, words=None, out=None, llr_dtype=None):

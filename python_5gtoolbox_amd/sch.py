@@ -11,6 +11,8 @@ one configuration — the C-ABI entry points ldpc5g_sch_* of include/ldpc5g.h.
         the received resource grid, channel estimate and covariance: phy.equalize first)
     sch_ml_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, ...) -> SchDecodeResult   (the same with a
         maximum-likelihood detector: phy.ml_detect, whose LLRs go straight to sch_decode_batch)
+    sch_ce_eq_rx_batch / sch_ce_ml_rx_batch(y, h_ls, ce, algo, re_idx, mod, cfg, L, ...)   (the same
+        from the DMRS least-squares estimate: phy.channel_estimate first)
 
 Device tensors in, device tensors out, everything asynchronous on the current stream; torch only
 allocates the buffers.  The per-transport-block drop-ins (nr_dlsch.DLSCHEncode,
@@ -386,6 +388,43 @@ def sch_ml_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, re_per_cov=12, cinit=N
     llr_dtype = t.float32 if kw.get("schedule") == "layered" else t.float64
     llr = phy.ml_detect(y, h, cov, mod, algo, re_idx, re_per_cov, cinit=cinit, llr_dtype=llr_dtype)
     return sch_decode_batch(llr, cfg, L, **kw)
+
+
+def _ce_stage(y, h_ls, ce):
+    """channel_estimate (and, with to_comp, the data REs' compensation) for the two chains below:
+    (y (T, R, Nr), h, cov), everything on the device and on the current stream."""
+    from . import phy
+    ce = dict(ce)
+    ce_algo = ce.pop("algo")
+    to_comp = bool(ce.get("to_comp", False))
+    T, R, Nr = y.shape
+    N, D = h_ls.shape[2], int(ce.get("re_distance", 4))
+    assert R == 14 * N * D, f"y has R = {R} resource elements, the slot has 14*N*D = {14 * N * D}"
+    if to_comp:
+        h, cov, extra = phy.channel_estimate(h_ls, algo=ce_algo, want=("to_avg",), **ce)
+        y = phy.to_compensate(y.reshape(T, 14, N * D, Nr), extra["to_avg"], ce["scs"]).view(T, R, Nr)
+    else:
+        h, cov = phy.channel_estimate(h_ls, algo=ce_algo, **ce)
+    return y, h, cov
+
+
+def sch_ce_eq_rx_batch(y, h_ls, ce, algo, re_idx, mod, cfg, L, **kw):
+    """The reference's receiver from (pdsch_resource, H_LS) to the transport block:
+    phy.channel_estimate, then sch_eq_rx_batch on its h and cov, with no host round trip between
+    the stages.  y: (T, 14*N*D, Nr) the slot's resource grid; h_ls: (T, S, N, Nr, Nt); ce: the
+    channel estimator's arguments as a dict (sym_map, algo, scs, eRB, l_left_ns, l_right_ns and
+    optionally re_distance, num_cdm_groups, to_comp — with to_comp the data REs are compensated
+    too, process_pdsch_data); algo, re_idx, mod, cfg, L and the keyword arguments as
+    sch_eq_rx_batch (re_per_cov is 12)."""
+    y, h, cov = _ce_stage(y, h_ls, ce)
+    return sch_eq_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, **kw)
+
+
+def sch_ce_ml_rx_batch(y, h_ls, ce, algo, re_idx, mod, cfg, L, **kw):
+    """sch_ce_eq_rx_batch for the maximum-likelihood detectors: phy.channel_estimate, then
+    sch_ml_rx_batch."""
+    y, h, cov = _ce_stage(y, h_ls, ce)
+    return sch_ml_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, **kw)
 
 
 # ------------------------------------------------------------ per-TB configurations (multi)
