@@ -576,6 +576,65 @@ int ldpc5g_to_compensate(const void* y, int64_t ldy, void* out, int64_t ldo, int
                          const double* to_avg, int32_t T, int64_t nsym, int64_t RE, int32_t Nr,
                          int32_t scs, void* stream);
 
+/* ================================================ slot front end (before the channel estimator)
+ * The producer of ldpc5g_channel_estimate's h_ls and of the equaliser's / detectors' y, from the
+ * frequency-domain slot grid rx_fd_slot_data that Pdsch.H_LS_est and Pdsch.RX_process take
+ * (py5gphy/nr_pdsch/nr_pdsch.py:212-284, 345-352), batched over T slots; and its transmit-side
+ * inverse.  DMRS configuration type 1, single-symbol DMRS, no SSB / CSI-RS / PDCCH in the slot (the
+ * reference's LS estimate does not handle them either, nr_pdsch_dmrs.py:193-194).
+ * Layout, per slot t (row strides ld* in COMPLEX elements, only the slot stride is free):
+ *   grid [t][r][s*carrier_re + k]   antenna-planar, s = 0..13, k = 0..carrier_re-1 subcarriers
+ *   h_ls [t][m][n][Nr][Nt]          ldpc5g_channel_estimate's input, m = 0..S-1, n = 0..N-1, N = 3*rb_size
+ *   y    [t][s*12*rb_size + re][Nr] the allocation's PRBs of all 14 symbols: ldpc5g_equalize's /
+ *                                   ldpc5g_ml_detect's y with R = 14*12*rb_size, ldpc5g_to_compensate's
+ *                                   y with nsym = 14, RE = 12*rb_size
+ * slots: T int32 slot numbers ON THE DEVICE; ports (Nt entries: PortIndexList[p] - 1000, in the
+ * caller's order) and sym_idx (S DMRS symbol indices) are HOST arrays read during the call.
+ *
+ * ldpc5g_slot_rx_frontend.  h_ls (pdsch_dmrs_LS_est, nr_pdsch_dmrs.py:196-219; pusch_dmrs_LS_est
+ * with transform precoding disabled, nr_pusch_dmrs.py:163-190): for DMRS RE n of port p0, delta =
+ * (p0 / 2) % 2, d0 = Y[4n + delta] conj(r(2n)), d1 = Y[4n + delta + 2] conj(r(2n + 1)), h_ls =
+ * (d0 + d1) / (2 scaling) for even p0 and (d0 - d1) / (2 scaling) for odd p0; scaling = 1 when
+ * num_cdm_groups == 1, else 10^(-3/20) (:170-174).  r is the QPSK mapping of the Gold sequence
+ * (nrPRBS.py:5-25) from bit 2 (6 rb_start + n) on, cinit = (((14 slot + sym + 1)(2 nNIDnSCID + 1)
+ * << 17) + 2 nNIDnSCID + nSCID) mod 2^31 (_gen_seq, :244-256), formed in the kernel from slots[t]
+ * and generated there by jump-ahead: no host sequence, no table upload.  y (copy_Rx_pdsch_resource,
+ * nrpdsch_resource_mapping.py:116-124) is a copy, bit for bit.  Either of h_ls / y may be NULL to
+ * skip that half.  in_dtype LDPC5G_F32 (complex64) or LDPC5G_F64 (complex128) is the type of grid,
+ * h_ls and y; the arithmetic is float64 for both (the reference multiplies in complex64).  At most
+ * two launches (one per output), asynchronous on `stream`, no allocation, no synchronisation, no
+ * atomics; results are bit-identical from run to run and a batch equals its slots run one by one.
+ *
+ * ldpc5g_slot_map (one launch).  sym [t][i*NL + l]: complex64 layer-interleaved modulated symbols
+ * of data RE i (ldpc5g_scramble_modulate's output; the layer mapping of nr_pdsch_process.py:27-32);
+ * re_idx: nre ascending flat indices s*12*rb_size + re of the data REs on the device (an index
+ * outside 0..14*12*rb_size-1 writes nothing); precoding: HOST array of num_ant*NL complex64
+ * (row-major [antenna][layer], interleaved re, im) or NULL for identity (needs NL <= num_ant).
+ * Layer l is port 1000 + l (the reference's transmit map indexes rows by port,
+ * nr_pdsch_dmrs.py:81-84).  Into the complex64 grid [t][a][.] it writes, for every antenna a,
+ *   - the DMRS of nr_pdsch_dmrs.py:90-120 (wf = [1, 1 - 2 (l % 2)], wt = 1), times float32(scaling),
+ *     precoded, at the REs 4n + delta and 4n + delta + 2 of the CDM groups that carry a layer;
+ *   - the precoded data sum_l w[a][l] sym[.][l] (float32, l ascending; nr_pdsch_process.py:34-42) at
+ *     the data REs (pdsch_data_re_mapping, nrpdsch_resource_mapping.py:58-85).
+ * Every other RE of the grid is left untouched (the caller zeroes it).
+ *
+ * Limits, all checked on the host BEFORE any HIP call (LDPC5G_ESIZE and a ldpc5g_last_error()
+ * message naming the argument): Nr, num_ant in {1, 2, 4}; 1 <= Nt, NL <= 4; ports in 0..3 and
+ * distinct; 1 <= S <= 4 with sym_idx strictly ascending in 0..13; carrier_re a multiple of 12 and
+ * carrier_re / 12 <= 275; 1 <= rb_size, 0 <= rb_start, rb_start + rb_size <= carrier_re / 12;
+ * nNIDnSCID in 0..65535, nSCID in 0..1, num_cdm_groups in 1..2; T in 1..65535; 0 <= nre <=
+ * 14*12*rb_size; a known in_dtype; row strides at least their rows; buffers aligned to their
+ * element size; non-null required buffers (both h_ls and y NULL is refused). */
+int ldpc5g_slot_rx_frontend(const void* grid, int64_t ldgrid, int32_t in_dtype, const int32_t* slots, int32_t T,
+                            int32_t carrier_re, int32_t rb_start, int32_t rb_size, int32_t Nr, int32_t Nt,
+                            const int32_t* ports, int32_t S, const int32_t* sym_idx, int32_t nNIDnSCID,
+                            int32_t nSCID, int32_t num_cdm_groups, void* h_ls, int64_t ldh, void* y, int64_t ldy,
+                            void* stream);
+int ldpc5g_slot_map(const void* sym, int64_t ldsym, const int32_t* re_idx, int64_t nre, const int32_t* slots,
+                    int32_t T, int32_t carrier_re, int32_t rb_start, int32_t rb_size, int32_t num_ant, int32_t NL,
+                    const float* precoding, int32_t S, const int32_t* sym_idx, int32_t nNIDnSCID, int32_t nSCID,
+                    int32_t num_cdm_groups, void* grid, int64_t ldgrid, void* stream);
+
 /* ================================================ gather records (multi-GPU)
  * Record r (a row of rec, stride ldr bytes) = the nbits int8 bits of row r of `bits` (values 0/1)
  * packed in np.packbits order (bit i -> byte i/8, bit 7 - i%8, tail zero-padded), then

@@ -151,6 +151,15 @@ SIGNATURES = {
     "ldpc5g_to_compensate": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
                                         _c.c_void_p, _c.c_int32, _c.c_int64, _c.c_int64, _c.c_int32,
                                         _c.c_int32, _c.c_void_p]),
+    "ldpc5g_slot_rx_frontend": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int32,
+                                           _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                           _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32,
+                                           _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
+                                           _c.c_void_p]),
+    "ldpc5g_slot_map": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                   _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                   _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
+                                   _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "ldpc5g_pack_records": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                        _c.c_void_p]),

@@ -13,6 +13,12 @@ entry points ldpc5g_prbs, ldpc5g_scramble_modulate, ldpc5g_demod_descramble (inc
         -> (h (T, 14*N*D, Nr, Nt), cov (T, 14*PRB, Nr, Nr))   (dft_dct_CE.py, dft_dct_symmetric_CE.py,
                                                               nr_channel_estimation.py:66-83,150-221)
     to_compensate(y (T, nsym, RE, Nr), to_avg (T,), scs)       (nr_channel_estimation.py:209-221)
+    slot_frontend(grid (T, Nr, 14*carrier_re), slots (T,), pdsch_config)
+        -> (h_ls (T, S, 3*RBSize, Nr, NL), y (T, 14*12*RBSize, Nr))   (nr_pdsch_dmrs.py:139-227,
+                                            nr_pusch_dmrs.py:107-200, nrpdsch_resource_mapping.py:87-129)
+    slot_map(sym (T, nre*NL), slots, pdsch_config, carrier_prbs, num_ant) -> grid (T, num_ant, 14*carrier_re)
+                        (nr_pdsch_dmrs.py:90-120, nr_pdsch_process.py:27-42, nrpdsch_resource_mapping.py:58-85)
+    dmrs_symlist(Ld, DMRSAddPos), slot_data_re_idx(pdsch_config) -> (re_idx, usage): host helpers
 mod: a MOD_ID value (the order Qm for QPSK..1024QAM, 1 BPSK, -1 pi/2-BPSK).
 Device tensors in and out; asynchronous on the current stream.
 """
@@ -281,3 +287,162 @@ def demod_descramble(sym, noise_var, mod, cinit=None, words=None, out=None, llr_
             _lib.F64 if llr.dtype == t.float64 else _lib.F32, llr.stride(0),
             _lib.stream_ptr(sym.device)))
     return llr
+
+
+# ------------------------------------------------------------------ the slot front end
+def dmrs_symlist(Ld, DMRSAddPos, channel="pdsch"):
+    """DMRS symbol indices of a mapping-type-A, single-symbol allocation whose last symbol is
+    Ld - 1: 38.211 Table 7.4.1.1.2-3 (nr_pdsch_dmrs.py:258-297, get_DMRS_symlist) and Table
+    6.4.1.1.3-3 with dmrs-TypeA-Position pos2 (nr_pusch_dmrs.py:251-286), which hold the same
+    entries."""
+    assert channel in ("pdsch", "pusch"), channel
+    assert 0 <= DMRSAddPos <= 3, f"DMRSAddPos {DMRSAddPos}"
+    if Ld <= 7 or DMRSAddPos == 0:
+        return [2]
+    if Ld <= 9:
+        return [2, 7]
+    if Ld <= 12:
+        return [[2, 9], [2, 6, 9], [2, 6, 9] if Ld <= 11 else [2, 5, 8, 11]][DMRSAddPos - 1]
+    return [[2, 11], [2, 7, 11], [2, 5, 8, 11]][DMRSAddPos - 1]
+
+
+def _slot_params(config):
+    """The fields of the reference's pdsch_config / pusch_config dict that the slot front end
+    uses, after the reference's own asserts (nr_pdsch_dmrs.py:155-165, nr_pusch_dmrs.py:127-142)."""
+    dm = config["DMRS"]
+    pusch = "nTransPrecode" in config
+    assert dm["DMRSConfigType"] == 1
+    assert dm["NrOfDMRSSymbols"] == 1
+    assert dm["PUSCHMappintType" if pusch else "PDSCHMappintType"] == "A"
+    assert dm["DMRSAddPos"] <= 3
+    nscid = int(dm["nSCID"])
+    if pusch:
+        assert dm["dmrs_TypeA_Position"] == "pos2"
+        if config["nTransPrecode"] != 0:
+            raise NotImplementedError("nTransPrecode != 0: transform precoding (the low-PAPR DMRS sequence, "
+                                      "nr_pusch_dmrs.py:216-228) is not provided")
+        nid = dm["transformPrecodingDisabled"]["NID0" if nscid == 0 else "NID1"]
+    else:
+        nid = dm["nNIDnSCID"]
+    NL = int(config["num_of_layers"])
+    start, nsym = int(config["StartSymbolIndex"]), int(config["NrOfSymbols"])
+    return dict(rb_start=int(config["ResAlloType1"]["RBStart"]), rb_size=int(config["ResAlloType1"]["RBSize"]),
+                NL=NL, ports=[int(p) for p in list(config["PortIndexList"])[:NL]], start=start, nsym=nsym,
+                symlist=dmrs_symlist(start + nsym, int(dm["DMRSAddPos"]), "pusch" if pusch else "pdsch"),
+                cdm=int(dm["NumCDMGroupsWithoutData"]), nid=int(nid), nscid=nscid, pusch=pusch)
+
+
+def slot_data_re_idx(pdsch_config):
+    """(re_idx, usage) of an allocation.  usage: copy_Rx_pdsch_resource's (NrOfSymbols, 12*RBSize)
+    float64 map, 1 where a DMRS symbol's RE is not available for data
+    (nrpdsch_resource_mapping.py:102-127): all twelve REs of a PRB when NumCDMGroupsWithoutData == 2,
+    otherwise the even REs if a used port is 1000 or 1001 and the odd REs if one is 1002 or 1003.
+    re_idx: the ascending int32 flat indices sym * 12*RBSize + re, over the slot's 14 symbols, of the
+    data REs (usage == 0) of symbols StartSymbolIndex .. StartSymbolIndex + NrOfSymbols - 1 — the
+    re_idx of equalize / ml_detect on slot_frontend's y.  Host arrays (numpy)."""
+    import numpy as np
+    p = _slot_params(pdsch_config)
+    prb = np.zeros(12)
+    if p["cdm"] == 2:
+        prb[:] = 1
+    else:
+        if 1000 in p["ports"] or 1001 in p["ports"]:
+            prb[0::2] = 1
+        if 1002 in p["ports"] or 1003 in p["ports"]:
+            prb[1::2] = 1
+    n = 12 * p["rb_size"]
+    usage = np.zeros((p["nsym"], n))
+    for s in p["symlist"]:
+        if p["start"] <= s < p["start"] + p["nsym"]:
+            usage[s - p["start"]] = np.tile(prb, p["rb_size"])
+    m, re = np.nonzero(usage == 0)
+    return ((m + p["start"]) * n + re).astype(np.int32), usage
+
+
+def slot_data_re_idx_device(pdsch_config, device):
+    """slot_data_re_idx's re_idx uploaded to `device`: a new tensor per call.  A caller that
+    receives many batches of one allocation uploads once and passes it as re_idx= to
+    sch.sch_slot_rx_batch / slot_map."""
+    _slot_params(pdsch_config)   # the reference's asserts come before any GPU work
+    t = _lib.require_gpu()
+    return t.from_numpy(slot_data_re_idx(pdsch_config)[0]).to(device)
+
+
+def _ld(x, T, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
+    return x.stride(0) if T > 1 else row
+
+
+def slot_frontend(grid, slots, pdsch_config, want=("h_ls", "y")):
+    """The received slot grids of T slots to the channel estimator's and the detectors' inputs
+    (ldpc5g_slot_rx_frontend; pdsch_dmrs_LS_est, nr_pdsch_dmrs.py:139-227, or pusch_dmrs_LS_est,
+    nr_pusch_dmrs.py:107-200, and copy_Rx_pdsch_resource, nrpdsch_resource_mapping.py:87-129).
+    grid: (T, Nr, 14*carrier_re) complex64 / complex128 device tensor, antenna-planar as the
+    reference's rx_fd_slot_data (only the slot stride is free); slots: (T,) int32 device tensor of
+    slot numbers; pdsch_config: the reference's pdsch_config (or pusch_config) dict.  Returns, in
+    the order of `want`, a tuple of h_ls (T, S, 3*RBSize, Nr, NL) — channel_estimate's input — and
+    y (T, 14*12*RBSize, Nr) — the allocation's PRBs of all 14 symbols, interleaved — of grid's dtype."""
+    assert want and all(w in ("h_ls", "y") for w in want), f"want {want!r}: a selection of 'h_ls', 'y'"
+    p = _slot_params(pdsch_config)   # the reference's asserts and refusals come before any GPU work
+    t = _lib.require_gpu()
+    assert grid.dim() == 3 and grid.dtype in (t.complex64, t.complex128) and grid[0].is_contiguous(), \
+        "grid: (T, Nr, 14*carrier_re) complex, only the slot stride is free"
+    T, Nr, W = grid.shape
+    assert W % 14 == 0, f"grid rows of {W} elements are not 14 symbols"
+    assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == grid.device
+    S, N, NL = len(p["symlist"]), 3 * p["rb_size"], p["NL"]
+    dev = grid.device
+    h_ls = t.empty((T, S, N, Nr, NL), dtype=grid.dtype, device=dev) if "h_ls" in want else None
+    y = t.empty((T, 14 * 4 * N, Nr), dtype=grid.dtype, device=dev) if "y" in want else None
+    ports = (_lib.ctypes.c_int32 * 4)(*[q - 1000 for q in p["ports"]])
+    syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
+    with t.cuda.device(dev):
+        _lib.check(_lib.lib().ldpc5g_slot_rx_frontend(
+            _lib.ptr(grid), _ld(grid, T, Nr * W), _lib.F32 if grid.dtype == t.complex64 else _lib.F64,
+            _lib.ptr(slots), T, W // 14, p["rb_start"], p["rb_size"], Nr, NL, ports, S, syms, p["nid"], p["nscid"],
+            p["cdm"], _lib.ptr(h_ls) if h_ls is not None else None, S * N * Nr * NL,
+            _lib.ptr(y) if y is not None else None, 14 * 4 * N * Nr, _lib.stream_ptr(dev)))
+    outs = {"h_ls": h_ls, "y": y}
+    return tuple(outs[w] for w in want)
+
+
+def slot_map(sym, slots, pdsch_config, carrier_prbs, num_ant, precoding=None, out=None, re_idx=None):
+    """The transmit-side inverse of slot_frontend (ldpc5g_slot_map; pdsch_dmrs_process,
+    nr_pdsch_dmrs.py:90-120, the precoding of nr_pdsch_process.py:27-42 and pdsch_data_re_mapping,
+    nrpdsch_resource_mapping.py:58-85).  sym: (T, nre*NL) complex64 layer-interleaved modulated
+    symbols (scramble_modulate's output), nre = len(slot_data_re_idx(pdsch_config)[0]); slots: (T,)
+    int32 device tensor; precoding: (num_ant, NL) array-like or None for identity.  Layers use ports
+    1000 .. 1000 + NL - 1 in order; re_idx: slot_data_re_idx_device's tensor, to save its upload.
+    Writes DMRS and data into out (T, num_ant, 14*12*carrier_prbs)
+    complex64 — every other RE is left as it is — or into a new zeroed grid, and returns it."""
+    import numpy as np
+    p = _slot_params(pdsch_config)
+    t = _lib.require_gpu()
+    NL = p["NL"]
+    assert p["ports"] == [1000 + l for l in range(NL)], \
+        f"PortIndexList {p['ports']}: the transmit map needs ports 1000..{999 + NL} in order (nr_pdsch_dmrs.py:81-84)"
+    dev = sym.device
+    if re_idx is None:
+        re_idx = slot_data_re_idx_device(pdsch_config, dev)
+    assert re_idx.dim() == 1 and re_idx.dtype == t.int32 and re_idx.is_contiguous() and re_idx.device == dev
+    nre = re_idx.shape[0]
+    assert sym.dim() == 2 and sym.dtype == t.complex64 and sym.stride(1) == 1
+    T = sym.shape[0]
+    assert sym.shape[1] == nre * NL, f"sym has {sym.shape[1]} symbols per slot, the allocation holds nre*NL = {nre}*{NL}"
+    assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == dev
+    W = 14 * 12 * int(carrier_prbs)
+    if out is None:
+        out = t.zeros((T, int(num_ant), W), dtype=t.complex64, device=dev)
+    assert out.dtype == t.complex64 and out.shape == (T, int(num_ant), W) and out[0].is_contiguous() and out.device == dev
+    pm = None
+    if precoding is not None:
+        w = np.ascontiguousarray(np.asarray(precoding, np.complex64)[:int(num_ant), :NL])
+        assert w.shape == (int(num_ant), NL), f"precoding {w.shape}: (num_ant, NL) wanted"
+        pm = w.view(np.float32).ctypes.data_as(_lib.ctypes.c_void_p)
+    S = len(p["symlist"])
+    syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
+    with t.cuda.device(dev):
+        _lib.check(_lib.lib().ldpc5g_slot_map(
+            _lib.ptr(sym), _ld(sym, T, nre * NL), _lib.ptr(re_idx), nre, _lib.ptr(slots), T, W // 14,
+            p["rb_start"], p["rb_size"], int(num_ant), NL, pm, S, syms, p["nid"], p["nscid"], p["cdm"],
+            _lib.ptr(out), _ld(out, T, int(num_ant) * W), _lib.stream_ptr(dev)))
+    return out

@@ -427,6 +427,31 @@ def sch_ce_ml_rx_batch(y, h_ls, ce, algo, re_idx, mod, cfg, L, **kw):
     return sch_ml_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, **kw)
 
 
+def sch_slot_rx_batch(grid, slots, pdsch_config, ce, algo, mod, cfg, L, re_idx=None, **kw):
+    """The reference's receiver from the slot grid to the transport block — Pdsch.H_LS_est,
+    NrChannelEstimation.channel_est and Pdsch.RX_process (nr_pdsch.py:212-284, 345-352) — for T
+    slots: phy.slot_frontend, then the channel estimator, then sch_eq_rx_batch (algo "ZF", "ZF-IRC",
+    "MMSE", "MMSE-IRC") or sch_ml_rx_batch (the ten ML names), all on the device and on the current
+    stream.  grid: (T, Nr, 14*carrier_re) complex64 / complex128 device tensor; slots: (T,) int32
+    device tensor; pdsch_config: the reference's dict; ce: the channel estimator's arguments as in
+    sch_ce_eq_rx_batch, whose sym_map and num_cdm_groups are filled in from pdsch_config; mod, cfg,
+    L and the keyword arguments as the chosen chain's; re_idx: phy.slot_data_re_idx_device's tensor
+    (uploaded here, once per call, when it is not given).  The data REs (phy.slot_data_re_idx) must
+    carry exactly the transport block: nre * NL * Qm == cfg.G."""
+    from . import phy
+    assert algo in _lib.EQ_ALGO or algo in _lib.ML_ALGO, \
+        f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO) + sorted(_lib.ML_ALGO)}"
+    h_ls, y = phy.slot_frontend(grid, slots, pdsch_config)
+    if re_idx is None:
+        re_idx = phy.slot_data_re_idx_device(pdsch_config, grid.device)
+    p = phy._slot_params(pdsch_config)
+    ce = dict(ce, sym_map=p["symlist"], num_cdm_groups=p["cdm"])
+    y, h, cov = _ce_stage(y, h_ls, ce)
+    if algo in _lib.EQ_ALGO:
+        return sch_eq_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, **kw)
+    return sch_ml_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, **kw)
+
+
 # ------------------------------------------------------------ per-TB configurations (multi)
 SchMultiResult = namedtuple(
     "SchMultiResult", "tb_ok tbblk llr_dn ck status iters cb_crc_ok tb_rem rows")
