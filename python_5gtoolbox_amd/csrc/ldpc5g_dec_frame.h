@@ -225,6 +225,14 @@ static_assert(kFrStr<1>.ok && kFrStr<2>.ok, "frame core-edge stream");
 #endif
 constexpr int kFrDA = LDPC5G_FR_DA, kFrDT = LDPC5G_FR_DT;
 static_assert(kFrDA >= 1 && kFrDT > kFrDA, "stream read distances");
+// The peeled iteration 0 (FIRST) is the first touch of the codeblock's extension LLRs and holds no
+// row state, so it has registers for a deeper ring of loads in flight than the loop's (kXPre = 4):
+// depths 8 / 12 / 16 measured 0.5 / 0.8 / 1.0 % of the 4096-codeblock launch.
+#ifndef LDPC5G_FR_XPRE_FIRST
+#define LDPC5G_FR_XPRE_FIRST 16
+#endif
+constexpr int kFrXPreFirst = LDPC5G_FR_XPRE_FIRST;
+static_assert(kFrXPreFirst >= 1, "ring depth");
 
 // V(i, k) mod Zc of edge k of row i; the same relative to the row's frame (thread s runs check node
 // s - off, so edge k's column entry is s + fr_cof); frame of LDS row i for half H's phase B

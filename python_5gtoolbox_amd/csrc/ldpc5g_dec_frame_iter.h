@@ -44,7 +44,8 @@
         uint64_t hdx = 0;   // hard decisions of the owned extension columns (LQ_old)
 
         // ext LLR ring: slot p % XP holds the LLR of the half's ext row p, loaded XP rows ahead
-        constexpr int XP = kXPre > 0 ? kXPre : 1;
+        // (FIRST: its own, deeper ring — those loads come from HBM, the loop's from L2)
+        constexpr int XP = FIRST ? kFrXPreFirst : kXPre > 0 ? kXPre : 1;
         T xr[XP];
         auto xload = [&](auto hc, auto pc_) {
             constexpr int hh = decltype(hc)::value, p = decltype(pc_)::value;

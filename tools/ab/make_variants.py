@@ -321,6 +321,40 @@ _REDERIVE_FLAGS = [
 #  in the copy; r04's lay_bitsyn diff was measured, rejected and deleted in r05: DESIGN.md §7)
 
 
+# instrumentation of the frame kernel (wrong ck rows): every workgroup records the real-time clock
+# (100 MHz) at 9 points — start, after the prologue's barrier, after the peeled iteration 0, after
+# iterations 1 and 2, loop exit, after the final pass's extension decisions, after its syndrome part
+# (and barrier), after the ck store — plus HW_ID and XCC_ID (which CU it ran on) into the first 88
+# bytes of its ck row (tools/frame_ts_probe.py reads them).  A 3-tuple patch names its own file.
+FRAME = "ldpc5g_dec_frame.h"
+FRAME_ITER = "ldpc5g_dec_frame_iter.h"
+_RT = "__builtin_amdgcn_s_memrealtime()"
+_FRAME_TS = [
+    ("    const int t = threadIdx.x;\n    const int h = __builtin_amdgcn_readfirstlane(t / Z);\n",
+     f"    const int t = threadIdx.x;\n    uint64_t ts[9] = {{}};\n    ts[0] = {_RT};\n"
+     "    const int h = __builtin_amdgcn_readfirstlane(t / Z);\n"),
+    ("    lds_barrier();\n    uint64_t live_x = ~0ull;\n", f"    lds_barrier();\n    ts[1] = {_RT};\n    uint64_t live_x = ~0ull;\n"),
+    ("    if (!active) {   // decided by the raw LLRs' syndrome\n",
+     f"    ts[2] = {_RT};\n    if (!active) {{   // decided by the raw LLRs' syndrome\n"),
+    (FRAME_ITER, "        if (!block_any(active)) break;\n    }\n",
+     f"        if (!FIRST && it == 1) ts[3] = {_RT};\n        if (!FIRST && it == 2) ts[4] = {_RT};\n"
+     "        if (!block_any(active)) break;\n    }\n"),
+    ("    int sv = s;\n    asm volatile(\"\" : \"+v\"(sv));   // keep the output addresses out of the loop\n",
+     f"    ts[5] = {_RT};\n    int sv = s;\n    asm volatile(\"\" : \"+v\"(sv));   // keep the output addresses out of the loop\n"),
+    ("        bool fail = false;\n        per_half([&](auto hc) {\n            constexpr int hh = decltype(hc)::value;\n            constexpr uint64_t rows = [] {",
+     f"        ts[6] = {_RT};\n        bool fail = false;\n        per_half([&](auto hc) {{\n"
+     "            constexpr int hh = decltype(hc)::value;\n            constexpr uint64_t rows = [] {"),
+    ("    lds_barrier();   // every LQ / state read is done: LDS below the flags is free from here\n",
+     f"    lds_barrier();   // every LQ / state read is done: LDS below the flags is free from here\n    ts[7] = {_RT};\n"),
+    ("    ck_store_staged(NFZ, 1, [&](int) -> int8_t* { return crow; }, slow, t, kFrThreads);\n}\n",
+     "    ck_store_staged(NFZ, 1, [&](int) -> int8_t* { return crow; }, slow, t, kFrThreads);\n"
+     f"    __syncthreads();\n    ts[8] = {_RT};\n"
+     "    if (t == 0) {\n        uint64_t* o = (uint64_t*)crow;\n        for (int k = 0; k < 9; ++k) o[k] = ts[k];\n"
+     "        o[9] = __builtin_amdgcn_s_getreg((31 << 11) | 4);\n        o[10] = __builtin_amdgcn_s_getreg((31 << 11) | 20);\n    }\n}\n"),
+]
+VARIANTS.update({"frame_ts": (FRAME, _FRAME_TS)})
+
+
 def make(name):
     target, patches = VARIANTS[name]
     d = os.path.join(ROOT, "build", "alt_src", name)
@@ -332,13 +366,31 @@ def make(name):
             r = subprocess.run(["patch", "-p3", "-d", d], stdin=f, capture_output=True, text=True)
         assert r.returncode == 0, (name, r.stdout, r.stderr)
     else:
-        s = open(p).read()
-        for old, new in patches:
+        for pt in patches:
+            q = os.path.join(d, pt[0]) if len(pt) == 3 else p
+            old, new = pt[-2:]
+            s = open(q).read()
             assert old in s, (name, old[:60])
-            s = s.replace(old, new)
-        open(p, "w").write(s)
+            open(q, "w").write(s.replace(old, new))
     out = os.path.join(ROOT, "build", "alt", name + ".so")
     os.makedirs(os.path.dirname(out), exist_ok=True)
+    if target == FRAME:
+        # the plain BG1 frame kernel's TU alone, linked with the product objects of the others
+        from python_5gtoolbox_amd import build as b
+        assert not os.environ.get("LDPC5G_EXTRA_FLAGS"), "the product objects must be built without A/B flags"
+        b.build(verbose=False)
+        od = os.path.join(ROOT, "build", "obj_alt_" + name)
+        os.makedirs(od, exist_ok=True)
+        tu = "ldpc5g_dec_frame1.hip"
+        try:
+            fo = b._compile(os.path.join(d, tu), False, od, d)
+        except subprocess.CalledProcessError as e:
+            return name, 1, str(e)
+        objs = [fo] + [os.path.join(b.OBJ, os.path.basename(x) + ".o") for x in b.sources()
+                       if os.path.basename(x) != tu]
+        r = subprocess.run([b.HIPCC, f"--offload-arch={b.ARCH}", "-shared", "-fPIC", *objs, "-o", out],
+                           capture_output=True, text=True)
+        return name, r.returncode, r.stderr[-2000:]
     if target == LAYERED and name.startswith("lay"):
         # only the layered TU instantiates the patched kernel: recompile it and link it with the
         # product objects of every other TU (build/obj, from the current product build)
