@@ -399,6 +399,24 @@ __device__ __forceinline__ void frame_body(
     // together all Zc entries of every row); a wave's ballots give one word (bit p: xlist row p
     // live) at the flags' offset 16 + 4 * wave, ORed per half after the prologue's barrier.
     static_assert(kFrThreads / 64 * 4 + 16 <= kFrFlagB, "per-wave liveness words in the flags");
+    // the first iteration runs peeled (FIRST) when columns 0 and 1 are punctured and the message
+    // alpha * max(0 - beta, 0) of a zero minimum is +-0 (any finite alpha).  It writes every
+    // state field itself, so the LDS state needs no zero fill then.  Not in the KDEAD kernels:
+    // a third copy of the iteration beside their two spills VGPRs to scratch (DESIGN.md 4.2e).
+    // BG1 (every row holds a punctured column) peels iteration 0 together with iteration 1's
+    // phase A (the fused start, ldpc5g_dec_frame_iter.h), which needs L >= 2; BG1 with L = 1 runs
+    // the general loop.
+    T zmsg = T(0);
+    if constexpr (OFS) {
+        zmsg = zmsg - beta;
+        zmsg = zmsg > T(0) ? zmsg : T(0);
+    }
+    // L = 0 runs no iteration at all: the final pass then reads the zero state filled below.
+    const bool peel = !KDEAD && L >= (BG == 1 ? 2 : 1) && pc == 2 && alpha * zmsg == T(0);
+    // the fused start keeps LLR + (+0.0) in the LQ image of columns >= 2 from the start: what
+    // iteration 0 leaves there (no -0.0).  x + (-0.0) = x for every x otherwise.
+    T zadd = -T(0);
+    if constexpr (BG == 1 && !KDEAD) zadd = peel ? T(0) : -T(0);
     {
         T v0[KH];
 #pragma unroll
@@ -427,21 +445,11 @@ __device__ __forceinline__ void frame_body(
 #pragma unroll
         for (int jj = 0; jj < KH; ++jj) {
             const int j = jcol(jj);
-            at((uint32_t)(j * kFrColB + s * 8)) = j < pc ? T(0) : v0[jj];
+            if constexpr (BG == 1 && !KDEAD) at((uint32_t)(j * kFrColB + s * 8)) = j < pc ? T(0) : v0[jj] + zadd;
+            else at((uint32_t)(j * kFrColB + s * 8)) = j < pc ? T(0) : v0[jj];
         }
         if (KDEAD && (t & 63) == 0) *(lds_u32*)(uintptr_t)(uint32_t)(kFrPlan<BG>.fl_b + 16 + (t >> 6) * 4) = wm;
     }
-    // the first iteration runs peeled (FIRST) when columns 0 and 1 are punctured and the message
-    // alpha * max(0 - beta, 0) of a zero minimum is +-0 (any finite alpha).  It writes every
-    // state field itself, so the LDS state needs no zero fill then.  Not in the KDEAD kernels:
-    // a third copy of the iteration beside their two spills VGPRs to scratch (DESIGN.md 4.2e).
-    T zmsg = T(0);
-    if constexpr (OFS) {
-        zmsg = zmsg - beta;
-        zmsg = zmsg > T(0) ? zmsg : T(0);
-    }
-    // L = 0 runs no iteration at all: the final pass then reads the zero state filled here.
-    const bool peel = !KDEAD && L >= 1 && pc == 2 && alpha * zmsg == T(0);
     for (int w = t; !peel && w < kFrPlan<BG>.nls * Z; w += kFrThreads) {
         V2<T> v;
         v.x = T(0), v.y = T(0);
@@ -477,11 +485,13 @@ __device__ __forceinline__ void frame_body(
     bool active = true;
     uint64_t hdx_keep = 0;   // extension decisions of a codeblock decided by the syndrome test
     int it = 0;
+    bool skipA = false;   // the loop's first trip finds its phase A done (BG1's fused start)
     if constexpr (!KDEAD) {
-        if (peel) {   // iteration 0 on the zero state
+        if (peel) {   // iteration 0 on the zero state (BG1: and iteration 1's phase A)
             constexpr bool FIRST = true, DEAD = false;
 #include "ldpc5g_dec_frame_iter.h"
         }
+        if constexpr (BG == 1) skipA = peel;
     }
     if (!active) {   // decided by the raw LLRs' syndrome
     } else if constexpr (KDEAD) {

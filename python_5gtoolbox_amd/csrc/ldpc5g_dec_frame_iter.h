@@ -21,9 +21,27 @@
 //    (+-mB) enters the register sum S.  With no LDS add there is no group barrier.
 //  - The syndrome flag is its own word (never reset): without phase-B barriers a reset of flagA
 //    could overtake another wave's read of it.
+//
+// FUSED (FIRST with BG1, where every row holds a punctured column; frame_body takes it for L >= 2):
+// iteration 0 together with iteration 1's phase A.  After iteration 0 every message into a column
+// >= 2 is +-0, so the LQ image of those columns is LLR + (+0.0) (the prologue stored that) and in
+// iteration 1 every edge but a row's first punctured one has r_old = +-0: |q| and q < 0 on the
+// non-punctured edges are what iteration 0 walked.
+//  - The pass (rowA_fused): each owned row in the zero-state form over its non-punctured edges;
+//    (min1', min2'), their sign word and argmin' are parked in the row's state slots.  Iteration
+//    0's own state is implicit: mA = alpha * clamp(0) = +-0, mB = alpha * clamp(min1'), idx = 0.
+//  - After the syndrome barrier: S = the row-ordered sum of +-mB over the rows with exactly one
+//    punctured column H (first_msg), T(0) + S into the image of column H, one barrier.
+//  - The combine (rowC): iteration 1's state of each owned row from the parked minima and its
+//    punctured edge(s), q_0 = (T(0) + S) - (+-mB), or the LQ entries themselves for a row with
+//    both (LQ - (+-0) = LQ, no image entry is -0.0).  The punctured edges come first in edge
+//    order and `aq < min1` is strict, so they keep the argmin on a tie.
+//  - The loop (FIRST = false) is then entered at it = 1 with skipA set: its first trip skips
+//    phase A and goes on at the barrier before the syndrome test.
 
     auto rdead = [&](int i) -> bool { return DEAD && i >= 4 && ((live_x >> (i - 4)) & 1u) == 0; };
     int* const flagI = FIRST ? flagA + 2 : flagA;
+    constexpr bool FUSED = FIRST && BG == 1;   // the fused start, see the top
     for (; it < (FIRST ? (L < 1 ? L : 1) : L); ++it) {
         // opaque per iteration: otherwise LICM hoists hundreds of loop-invariant addresses
         uint32_t sb = sb0, sbw = sbw0, tz = tz0;
@@ -42,6 +60,8 @@
         auto llrx = [&](int i) -> T { return ldg(lrow_x, i * Z + xpos(i)); };
         bool fail = false;
         uint64_t hdx = 0;   // hard decisions of the owned extension columns (LQ_old)
+        const bool runA = FIRST || !skipA;   // after the fused start: iteration 1's state is there,
+        if (!runA) hdx = hdx_keep;           // and its decisions are those of the start's pass
 
         // ext LLR ring: slot p % XP holds the LLR of the half's ext row p, loaded XP rows ahead
         // (FIRST: its own, deeper ring — those loads come from HBM, the loop's from L2)
@@ -221,7 +241,84 @@
             });
             put_first(ic, par, min1, min2, negs, idx);
         };
-        if (active) {
+        // FUSED, the pass: the zero-state row over its non-punctured edges.  It parks the raw
+        // (min1', min2'), their sign word and argmin' in the row's state slots.
+        auto rowA_fused = [&](auto ic) {
+            constexpr int i = decltype(ic)::value, e0 = P::RS[i], d = kFrPlan<BG>.deg(i);
+            constexpr int npun = (kFrPlan<BG>.kc[0][i] >= 0) + (kFrPlan<BG>.kc[1][i] >= 0);
+            static_assert(!FUSED || npun >= 1, "every row of the fused start holds a punctured column");
+            T min1 = FT<T>::inf(), min2 = FT<T>::inf();
+            uint32_t idx = 0, negs = 0;   // the punctured edges come first and shift in zeros
+            bool par = false;
+            sfor<0, d>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                if constexpr (P::COL[e0 + k] < 2) {
+                    static_assert(k < npun, "punctured edges first");
+                    sskip(ic, kc);
+                } else {
+                    const T a = edge0(ic, kc);
+                    par ^= a < T(0);
+                    const T aq = fabs(a);
+                    idx = aq < min1 ? (uint32_t)k : idx;
+                    asm volatile("" : "+v"(idx));
+                    negs = __builtin_amdgcn_alignbit(negs, FT<T>::sbits(a), 31);
+                    two_min(min1, min2, aq);
+                }
+            });
+            fail |= par;
+            put_state(ic, min1, min2, negs, idx);
+        };
+        // FUSED: iteration 0's message to the row's single punctured column, +-mB, from the parked
+        // min1' and sign word (edge 0's own sign bit is 0, so its sign is the row's sign product);
+        // alpha * max(x - beta, 0) as in put_first
+        auto first_msg = [&](T x, uint32_t negs) -> T {
+            if constexpr (OFS) {
+                x = x - beta;
+                x = x > T(0) ? x : T(0);
+            }
+            return xsign_v(alpha * x, (uint32_t)__builtin_popcount(negs) << 31, mv);
+        };
+        // FUSED, the combine: iteration 1's state of the row from the parked minima and the
+        // punctured edge(s).  lqo: this thread's entry of its half's punctured column, T(0) + S.
+        // An image entry is LLR + (+0.0) or T(0) + S, never -0.0, so its sign bit is its `< 0`,
+        // the parked word's parity is the parity of the non-punctured edges, and
+        // LQ - (+-0) = LQ bit for bit on the edges of a row with both punctured columns.
+        auto rowC = [&](auto ic, T lqo) {
+            constexpr int i = decltype(ic)::value, e0 = P::RS[i], d = kFrPlan<BG>.deg(i);
+            constexpr int npun = (kFrPlan<BG>.kc[0][i] >= 0) + (kFrPlan<BG>.kc[1][i] >= 0);
+            T m1, m2;
+            uint32_t u, idx;
+            get_state(ic, m1, m2, u, idx);
+            uint32_t negs = u >> (32 - d);
+            bool par = __builtin_popcount(negs) & 1u;
+            auto lqp = [&](auto kc) -> T {   // LQ of the punctured edge k
+                constexpr int k = decltype(kc)::value, j = P::COL[e0 + k], c = fr_cof<BG>(i, k);
+                static_assert(j < 2 && k < npun, "punctured edges first");
+                if constexpr (j == kFrPlan<BG>.owner[i] && c == 0) return lqo;
+                else return at((uint32_t)(j * kFrColB) + rot(c));
+            };
+            if constexpr (npun == 1) {
+                const T a0 = lqp(std::integral_constant<int, 0>{});
+                const T q0 = a0 - first_msg(m1, negs);
+                const T aq0 = fabs(q0);
+                par ^= a0 < T(0);
+                idx = m1 < aq0 ? idx : 0u;   // edge 0 comes first: it keeps the argmin on a tie
+                two_min(m1, m2, aq0);
+                negs |= (FT<T>::sbits(q0) >> 31) << (d - 1);
+            } else {
+                const T a0 = lqp(std::integral_constant<int, 0>{}), a1 = lqp(std::integral_constant<int, 1>{});
+                const T aq0 = fabs(a0), aq1 = fabs(a1);
+                par ^= a0 < T(0);
+                par ^= a1 < T(0);
+                idx = m1 < aq1 ? idx : 1u;
+                idx = fmin(m1, aq1) < aq0 ? idx : 0u;
+                two_min(m1, m2, aq0);
+                two_min(m1, m2, aq1);
+                negs |= ((FT<T>::sbits(a0) >> 31) << (d - 1)) | ((FT<T>::sbits(a1) >> 31) << (d - 2));
+            }
+            put_first(ic, par, m1, m2, negs, idx);
+        };
+        if (active && runA) {
             per_half([&](auto hc) {
                 sfor<0, XP>([&](auto pc_) { xload(hc, pc_); });
                 sfor<0, kFrDT>([&](auto pc_) { sload_t(hc, pc_); });
@@ -230,7 +327,9 @@
             sfor<0, MB>([&](auto ic) {   // one branch per row: bounded live ranges
                 constexpr int i = decltype(ic)::value;
                 if (h == kFrPlan<BG>.owner[i]) {
-                    if constexpr (FIRST) {
+                    if constexpr (FUSED) {
+                        rowA_fused(ic);
+                    } else if constexpr (FIRST) {
                         if constexpr (fr_punct<BG>(i)) rowA_punct(ic);
                         else rowA_zero(ic);
                     } else if constexpr (DEAD && i >= 4) {
@@ -267,14 +366,51 @@
         T S = T(0);
         // the core LLRs of the LQ update, loaded now so phase B hides their latency
         T lf[KH];
-        if (active) {
+        if (!FUSED && active) {   // FUSED: the image of columns >= 2 holds LLR + (+0.0) already
 #pragma unroll
             for (int jj = 0; jj < KH; ++jj) {
                 const int j = jcol(jj);
                 lf[jj] = ldg(lrow, (j < pc ? 0 : j - pc) * Z + sv);
             }
         }
-        if constexpr (FIRST) {
+        if constexpr (FUSED) {
+            // iteration 0's column sums: rows in order, a row with one punctured column H gives S
+            // its message (from the parked min1'); every other message is +-0 and is dropped
+            T lqo = T(0);
+            if (active) {
+                hdx_keep = hdx;   // iteration 1 decides on the same LLR + (+0.0) entries
+                per_half([&](auto hc) {
+                    constexpr int H = decltype(hc)::value;
+                    sfor<0, MB>([&](auto ic) {
+                        constexpr int i = decltype(ic)::value, d = kFrPlan<BG>.deg(i);
+                        if constexpr (kFrPlan<BG>.kc[H][i] >= 0 && !kFrPlan<BG>.both(i)) {
+                            static_assert(kFrPlan<BG>.kc[H][i] == 0, "the punctured edge first");
+                            T a, b;
+                            uint32_t u, idx;
+                            if constexpr (kFrPlan<BG>.lds[i]) {
+                                lds_get(ic, rot((Z - fr_pf<BG>(i, H)) % Z), a, b, u, idx);
+                            } else {
+                                static_assert(kFrPlan<BG>.owner[i] == H && kFrPlan<BG>.fr[i] == H, "own frame");
+                                get_state(ic, a, b, u, idx);
+                            }
+                            S = S + first_msg(a, u >> (32 - d));
+                        }
+                    });
+                });
+                lqo = T(0) + S;   // punctured columns: LLR 0 (:43)
+                at((uint32_t)(h * kFrColB) + sb) = lqo;
+            }
+            lds_barrier();
+            // ---- iteration 1's phase A: each owned row's parked minima and its punctured edge(s)
+            fail = false;
+            if (active) {
+                sfor<0, MB>([&](auto ic) {
+                    if (h == kFrPlan<BG>.owner[decltype(ic)::value]) rowC(ic, lqo);
+                });
+                if (fail) *flagA = 1;   // read after the loop's first barrier
+            }
+        }
+        if constexpr (FIRST && !FUSED) {
             // rows in order: a row with one punctured column H gives S its message (+-mB); a row
             // with both sends only +-0; a row with none adds as in the general code, then a barrier
             // (its columns may meet the next such row's)
@@ -402,5 +538,7 @@
             }
         }
         if (!FIRST && t == 0) *flagA = 0;   // read before the phase-B barriers
-        if (!block_any(active)) break;
+        if constexpr (!FIRST) skipA = false;
+        // FUSED: the loop's first trip begins with the barrier (its phase A is done above)
+        if (FUSED ? !active : !block_any(active)) break;
     }

@@ -322,37 +322,59 @@ _REDERIVE_FLAGS = [
 
 
 # instrumentation of the frame kernel (wrong ck rows): every workgroup records the real-time clock
-# (100 MHz) at 9 points — start, after the prologue's barrier, after the peeled iteration 0, after
-# iterations 1 and 2, loop exit, after the final pass's extension decisions, after its syndrome part
+# (100 MHz) at 9 points — start, after the prologue's barrier, after the peeled iteration 0 (BG1:
+# the fused start, iteration 0 and iteration 1's phase A), after iterations 1 (BG1: its phase B
+# alone) and 2, loop exit, after the final pass's extension decisions, after its syndrome part
 # (and barrier), after the ck store — plus HW_ID and XCC_ID (which CU it ran on) into the first 88
-# bytes of its ck row (tools/frame_ts_probe.py reads them).  A 3-tuple patch names its own file.
+# bytes of its ck row; frame_ts_fused adds two stamps inside the fused start, in the 16 bytes behind
+# (tools/frame_ts_probe.py reads them).  A 3-tuple patch names its own file.
 FRAME = "ldpc5g_dec_frame.h"
 FRAME_ITER = "ldpc5g_dec_frame_iter.h"
 _RT = "__builtin_amdgcn_s_memrealtime()"
-_FRAME_TS = [
-    ("    const int t = threadIdx.x;\n    const int h = __builtin_amdgcn_readfirstlane(t / Z);\n",
-     f"    const int t = threadIdx.x;\n    uint64_t ts[9] = {{}};\n    ts[0] = {_RT};\n"
-     "    const int h = __builtin_amdgcn_readfirstlane(t / Z);\n"),
-    ("    lds_barrier();\n    uint64_t live_x = ~0ull;\n", f"    lds_barrier();\n    ts[1] = {_RT};\n    uint64_t live_x = ~0ull;\n"),
-    ("    if (!active) {   // decided by the raw LLRs' syndrome\n",
-     f"    ts[2] = {_RT};\n    if (!active) {{   // decided by the raw LLRs' syndrome\n"),
-    (FRAME_ITER, "        if (!block_any(active)) break;\n    }\n",
-     f"        if (!FIRST && it == 1) ts[3] = {_RT};\n        if (!FIRST && it == 2) ts[4] = {_RT};\n"
-     "        if (!block_any(active)) break;\n    }\n"),
-    ("    int sv = s;\n    asm volatile(\"\" : \"+v\"(sv));   // keep the output addresses out of the loop\n",
-     f"    ts[5] = {_RT};\n    int sv = s;\n    asm volatile(\"\" : \"+v\"(sv));   // keep the output addresses out of the loop\n"),
-    ("        bool fail = false;\n        per_half([&](auto hc) {\n            constexpr int hh = decltype(hc)::value;\n            constexpr uint64_t rows = [] {",
-     f"        ts[6] = {_RT};\n        bool fail = false;\n        per_half([&](auto hc) {{\n"
-     "            constexpr int hh = decltype(hc)::value;\n            constexpr uint64_t rows = [] {"),
-    ("    lds_barrier();   // every LQ / state read is done: LDS below the flags is free from here\n",
-     f"    lds_barrier();   // every LQ / state read is done: LDS below the flags is free from here\n    ts[7] = {_RT};\n"),
-    ("    ck_store_staged(NFZ, 1, [&](int) -> int8_t* { return crow; }, slow, t, kFrThreads);\n}\n",
-     "    ck_store_staged(NFZ, 1, [&](int) -> int8_t* { return crow; }, slow, t, kFrThreads);\n"
-     f"    __syncthreads();\n    ts[8] = {_RT};\n"
-     "    if (t == 0) {\n        uint64_t* o = (uint64_t*)crow;\n        for (int k = 0; k < 9; ++k) o[k] = ts[k];\n"
-     "        o[9] = __builtin_amdgcn_s_getreg((31 << 11) | 4);\n        o[10] = __builtin_amdgcn_s_getreg((31 << 11) | 20);\n    }\n}\n"),
-]
-VARIANTS.update({"frame_ts": (FRAME, _FRAME_TS)})
+
+
+def _frame_ts(inner):
+    p = [
+        ("    const int t = threadIdx.x;\n    const int h = __builtin_amdgcn_readfirstlane(t / Z);\n",
+         f"    const int t = threadIdx.x;\n    uint64_t ts[{11 if inner else 9}] = {{}};\n    ts[0] = {_RT};\n"
+         "    const int h = __builtin_amdgcn_readfirstlane(t / Z);\n"),
+        ("    lds_barrier();\n    uint64_t live_x = ~0ull;\n", f"    lds_barrier();\n    ts[1] = {_RT};\n    uint64_t live_x = ~0ull;\n"),
+        ("    if (!active) {   // decided by the raw LLRs' syndrome\n",
+         f"    ts[2] = {_RT};\n    if (!active) {{   // decided by the raw LLRs' syndrome\n"),
+        (FRAME_ITER, "        if (FUSED ? !active : !block_any(active)) break;\n    }\n",
+         f"        if (!FIRST && it == 1) ts[3] = {_RT};\n        if (!FIRST && it == 2) ts[4] = {_RT};\n"
+         "        if (FUSED ? !active : !block_any(active)) break;\n    }\n"),
+        ("    int sv = s;\n    asm volatile(\"\" : \"+v\"(sv));   // keep the output addresses out of the loop\n",
+         f"    ts[5] = {_RT};\n    int sv = s;\n    asm volatile(\"\" : \"+v\"(sv));   // keep the output addresses out of the loop\n"),
+        ("        bool fail = false;\n        per_half([&](auto hc) {\n            constexpr int hh = decltype(hc)::value;\n            constexpr uint64_t rows = [] {",
+         f"        ts[6] = {_RT};\n        bool fail = false;\n        per_half([&](auto hc) {{\n"
+         "            constexpr int hh = decltype(hc)::value;\n            constexpr uint64_t rows = [] {"),
+        ("    lds_barrier();   // every LQ / state read is done: LDS below the flags is free from here\n",
+         f"    lds_barrier();   // every LQ / state read is done: LDS below the flags is free from here\n    ts[7] = {_RT};\n"),
+        ("    ck_store_staged(NFZ, 1, [&](int) -> int8_t* { return crow; }, slow, t, kFrThreads);\n}\n",
+         "    ck_store_staged(NFZ, 1, [&](int) -> int8_t* { return crow; }, slow, t, kFrThreads);\n"
+         f"    __syncthreads();\n    ts[8] = {_RT};\n"
+         "    if (t == 0) {\n        uint64_t* o = (uint64_t*)crow;\n        for (int k = 0; k < 9; ++k) o[k] = ts[k];\n"
+         "        o[9] = __builtin_amdgcn_s_getreg((31 << 11) | 4);\n        o[10] = __builtin_amdgcn_s_getreg((31 << 11) | 20);\n"
+         + ("        o[11] = ts[9], o[12] = ts[10];\n" if inner else "") + "    }\n}\n"),
+    ]
+    if inner:
+        p += [
+            # BG1's fused start (stamp 2 is its end): after the pass and its barrier, after the column sums
+            # of iteration 0 and their barrier (the combine follows); written behind HW_ID / XCC_ID
+            (FRAME_ITER, "        lds_barrier();\n        // ---- the syndrome of LQ_old decides (:107-114): output its hard decisions\n",
+             f"        lds_barrier();\n        if constexpr (FUSED) ts[9] = {_RT};\n"
+             "        // ---- the syndrome of LQ_old decides (:107-114): output its hard decisions\n"),
+            (FRAME_ITER, "            lds_barrier();\n            // ---- iteration 1's phase A: each owned row's parked minima",
+             f"            lds_barrier();\n            ts[10] = {_RT};\n"
+             "            // ---- iteration 1's phase A: each owned row's parked minima"),
+        ]
+    return p
+
+
+# frame_ts_fused: also the two stamps inside the fused start (their four SGPRs cost the plain BG1
+# kernel 44 B/lane of scratch, which slows its steady iterations: read only the start's split there)
+VARIANTS.update({"frame_ts": (FRAME, _frame_ts(False)), "frame_ts_fused": (FRAME, _frame_ts(True))})
 
 
 def make(name):

@@ -1,7 +1,8 @@
 """Per-workgroup phase timing of the float64 frame kernel (dev tool): run with
 LDPC5G_LIB=build/alt/frame_ts.so (tools/ab/make_variants.py frame_ts), whose workgroups write 9
 real-time clock stamps (100 MHz) and their HW_ID / XCC_ID registers into the first 88 bytes of
-their ck row.  Prints the split and writes it as JSON.
+their ck row; the frame_ts_fused build adds two stamps inside BG1's fused start in the 16 bytes
+behind.  Prints the split and writes it as JSON.
 
     LDPC5G_LIB=build/alt/frame_ts.so python tools/frame_ts_probe.py [B] [L] [out.json]
 """
@@ -37,8 +38,11 @@ def main():
         D.nr_decode_ldpc_batch(llr, Zc, 1, L, "min-sum", 0.75, 0.0, "flooding", out=out)
     torch.cuda.synchronize()
     assert int(out[2].min()) == L, "a codeblock left the loop early: the split assumes L iterations"
-    raw = out[0][:, :88].contiguous().cpu().numpy().view(np.uint64).astype(np.int64)   # [B, 11]
+    raw = out[0][:, :104].contiguous().cpu().numpy().view(np.uint64).astype(np.int64)   # [B, 13]
     ts = raw[:, :9]
+    # the fused start's inner stamps (a build without them leaves decoded bits there)
+    inner = raw[:, 11:13]
+    fused = bool(((ts[:, 1] <= inner[:, 0]) & (inner[:, 0] <= inner[:, 1]) & (inner[:, 1] <= ts[:, 2])).all())
     cu = ((raw[:, 9] >> 8) & 0xff) | ((raw[:, 10] & 0xf) << 8)   # CU / SH / SE bits of HW_ID, XCC
     d = np.diff(ts, axis=1) * 10e-3   # us
     life = (ts[:, 8] - ts[:, 0]) * 10e-3
@@ -60,12 +64,22 @@ def main():
                                "min": round(float(d[:, k].min()), 3), "max": round(float(d[:, k].max()), 3)}
         print(f"  {n:26s} mean {d[:, k].mean():8.2f} us  median {np.median(d[:, k]):8.2f}  min {d[:, k].min():8.2f}  max {d[:, k].max():8.2f}")
     print(f"  {'gap to the CU next WG':26s} mean {gaps.mean():8.2f} us  median {np.median(gaps):8.2f}  min {gaps.min():8.2f}  max {gaps.max():8.2f}")
-    steady = float(d[:, 3].mean())
-    fixed = float(d[:, 0].mean() + (d[:, 1].mean() - 0.28 * steady) + d[:, 5].mean() + d[:, 6].mean() + d[:, 7].mean() + gaps.mean())
-    res["fixed_cost_us"] = round(fixed, 3)
-    res["fixed_cost_share_of_life_plus_gap"] = round(fixed / float(life.mean() + gaps.mean()), 4)
-    print(f"  fixed cost (prologue + it0 - 0.28 steady + final + ck + gap) = {fixed:.2f} us = "
-          f"{100 * res['fixed_cost_share_of_life_plus_gap']:.1f} % of life + gap")
+    # BG1's fused start: "iteration 0 (peeled)" is iteration 0 with iteration 1's phase A, and
+    # "iteration 1" its phase B alone, so the fixed-cost formula of the peeled iteration has no meaning
+    res["fused_start"] = bool(d[:, 2].mean() < 0.75 * d[:, 3].mean())
+    if fused:
+        parts = np.stack([inner[:, 0] - ts[:, 1], inner[:, 1] - inner[:, 0], ts[:, 2] - inner[:, 1]], axis=1) * 10e-3
+        res["fused_start_us"] = {}
+        for k, n in enumerate(["pass + barrier", "iteration 0's column sums + barrier", "combine"]):
+            res["fused_start_us"][n] = round(float(parts[:, k].mean()), 3)
+            print(f"    fused start: {n:36s} mean {parts[:, k].mean():8.2f} us")
+    elif not res["fused_start"]:
+        steady = float(d[:, 3].mean())
+        fixed = float(d[:, 0].mean() + (d[:, 1].mean() - 0.28 * steady) + d[:, 5].mean() + d[:, 6].mean() + d[:, 7].mean() + gaps.mean())
+        res["fixed_cost_us"] = round(fixed, 3)
+        res["fixed_cost_share_of_life_plus_gap"] = round(fixed / float(life.mean() + gaps.mean()), 4)
+        print(f"  fixed cost (prologue + it0 - 0.28 steady + final + ck + gap) = {fixed:.2f} us = "
+              f"{100 * res['fixed_cost_share_of_life_plus_gap']:.1f} % of life + gap")
     if dst:
         os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
         with open(dst, "w") as f:
