@@ -635,6 +635,74 @@ int ldpc5g_slot_map(const void* sym, int64_t ldsym, const int32_t* re_idx, int64
                     const float* precoding, int32_t S, const int32_t* sym_idx, int32_t nNIDnSCID, int32_t nSCID,
                     int32_t num_cdm_groups, void* grid, int64_t ldgrid, void* stream);
 
+/* ================================================ PUSCH transform precoding (DFT-s-OFDM)
+ * The nTransPrecode = 1 branch of the reference's PUSCH, batched over T slots: the spreading DFT
+ * (nr_pusch_process.py:39-54), the de-spreading IDFT before demodulation (nr_pusch.py:170-194),
+ * the low-PAPR DMRS sequence (common/lowPAPR_seq.py:5-41) with its group / sequence hopping
+ * (nr_pusch_dmrs.py:216-249), and the slot front end and transmit map that use it.  One layer
+ * (the reference asserts it, nr_pusch_process.py:45), NumCDMGroupsWithoutData = 2 (with 1 the
+ * reference's own assert at nr_pusch.py:179 fails), DMRS configuration type 1, single-symbol DMRS.
+ * rb_size must be 2^a 3^b 5^c (38.211 6.3.1.4).  Row strides in COMPLEX elements; in_dtype
+ * LDPC5G_F32 (complex64) or LDPC5G_F64 (complex128) is the storage type, the arithmetic is float64
+ * for both and the complex64 result is the complex128 result rounded, bit for bit.  Every call is
+ * asynchronous on `stream`, with no allocation, no synchronisation and no atomics; results are
+ * bit-identical from run to run and a batch equals its rows run one by one.
+ *
+ * ldpc5g_transform_precode (one launch).  x [t][s*M + k], s < nsym, M = 12 rb_size: every M-block
+ * is transformed on its own.  inverse = 0: out = DFT(x) / sqrt(M) (np.fft.fft(.) / sqrt(M),
+ * nr_pusch_process.py:53); inverse = 1: out = IDFT(x) sqrt(M) (np.fft.ifft(.) * sqrt(M),
+ * nr_pusch.py:188): both orthonormal.  out may equal x (in place, then ldo == ldx); any other
+ * overlap is undefined.  A mixed-radix Stockham transform in LDS (radix 3, 5, 4, 2 passes), twiddles
+ * from a table of sincospi(2 j / M) indexed by an exact integer.  Limits: T in 1..65535, nsym in
+ * 1..14, rb_size in 1..275 and 2^a 3^b 5^c, inverse in 0..1, strides at least nsym*M, buffers
+ * non-null and aligned to their element size.
+ *
+ * ldpc5g_low_papr_seq (one launch).  u, v: n int32 each ON THE DEVICE (group number 0..29, base
+ * sequence number 0..1; v = 0 for MZC < 72); out [n][MZC] complex128 = exp(j alpha m) rbar_{u,v}(m)
+ * of gen_lowPAPR_seq (lowPAPR_seq.py:5-41).  MZC = 30: exp(-j pi (u+1)(m+1)(m+2) / 31) (:30).
+ * MZC >= 36: x_q(m mod N_ZC), x_q(i) = exp(-j pi q i (i+1) / N_ZC) (:32-38), N_ZC the largest prime
+ * below MZC (found on the host), q = floor(qbar + 1/2) + v (-1)^floor(2 qbar), qbar = N_ZC (u+1) /
+ * 31, all from integers; the phase index q i (i+1) is reduced mod 2 N_ZC in 64-bit integers before
+ * the one sincospi (the reference evaluates pi q i (i+1) / N_ZC in floating point at arguments up
+ * to ~1e7 rad and sits up to 2e-9 away).  Limits: n in 1..65535; MZC a multiple of 6 in 30..3300 —
+ * MZC in {6, 12, 18, 24} are the tables of 38.211 5.2.2.2, not provided, and refused; alpha finite.
+ *
+ * ldpc5g_slot_rx_frontend_tp: ldpc5g_slot_rx_frontend for pusch_dmrs_LS_est with nTransPrecode = 1
+ * (nr_pusch_dmrs.py:163-190): one layer on port `port` (0..3; delta and the sign of d1 as above),
+ * scaling 10^(-3/20), h_ls [t][m][n][Nr][1]; y by ldpc5g_slot_rx_frontend's extraction.  The
+ * sequence of (t, m) has alpha = 0 and length 6 rb_size and is formed in the kernel from slots[t]
+ * and sym_idx[m] (_gen_seq_with_transform_precoding, :216-249):
+ *   hopping 0 (neither):  u = nPuschID % 30, v = 0
+ *   hopping 1 (group):    f_gh = (sum_{i<8} 2^i c(8 (14 slot + sym) + i)) mod 30 with cinit =
+ *                         floor(nPuschID / 30); u = (f_gh + nPuschID) % 30, v = 0       (:230-239)
+ *   hopping 2 (sequence): u = nPuschID % 30; v = c(14 slot + sym) with cinit = nPuschID (as the
+ *                         reference has it) when 6 rb_size >= 72, else 0                  (:223-225, 241-249)
+ * with the Gold bits by jump-ahead (no host sequence); slots[t] in 0..19 (the reference makes one
+ * frame of hopping bits).  base_seq: optional complex128 [T][S][6 rb_size] ON THE DEVICE that
+ * replaces the generated sequence; required (NULL refused) when rb_size <= 4.  Limits: those of
+ * ldpc5g_slot_rx_frontend, and port in 0..3, nPuschID in 0..1007, hopping in 0..2, rb_size of the
+ * form 2^a 3^b 5^c.  At most two launches.
+ *
+ * ldpc5g_slot_map_tp (one launch): ldpc5g_slot_map for the same case.  sym [t][i]: the complex64
+ * (already transform-precoded) symbol of data RE i; precoding: HOST array of num_ant complex64
+ * ([antenna][0], interleaved re, im) or NULL for identity (antenna 0 carries the layer, the others
+ * zeros); base_seq as above.  Into the complex64 grid it writes float32(scaling r(2n)) at RE 4n +
+ * delta and float32(+- scaling r(2n+1)) at 4n + delta + 2 of every DMRS symbol (nr_pusch_dmrs.py:76-101;
+ * the other comb stays untouched), and the data at the data REs, both precoded with float32
+ * products.  Limits: those of ldpc5g_slot_map with NL = 1, and the ones above. */
+int ldpc5g_transform_precode(const void* x, int64_t ldx, void* out, int64_t ldo, int32_t in_dtype, int32_t T,
+                             int32_t nsym, int32_t rb_size, int32_t inverse, void* stream);
+int ldpc5g_low_papr_seq(const int32_t* u, const int32_t* v, int32_t n, double alpha, int32_t MZC, void* out,
+                        void* stream);
+int ldpc5g_slot_rx_frontend_tp(const void* grid, int64_t ldgrid, int32_t in_dtype, const int32_t* slots, int32_t T,
+                               int32_t carrier_re, int32_t rb_start, int32_t rb_size, int32_t Nr, int32_t port,
+                               int32_t S, const int32_t* sym_idx, int32_t nPuschID, int32_t hopping,
+                               const void* base_seq, void* h_ls, int64_t ldh, void* y, int64_t ldy, void* stream);
+int ldpc5g_slot_map_tp(const void* sym, int64_t ldsym, const int32_t* re_idx, int64_t nre, const int32_t* slots,
+                       int32_t T, int32_t carrier_re, int32_t rb_start, int32_t rb_size, int32_t num_ant, int32_t port,
+                       const float* precoding, int32_t S, const int32_t* sym_idx, int32_t nPuschID, int32_t hopping,
+                       const void* base_seq, void* grid, int64_t ldgrid, void* stream);
+
 /* ================================================ gather records (multi-GPU)
  * Record r (a row of rec, stride ldr bytes) = the nbits int8 bits of row r of `bits` (values 0/1)
  * packed in np.packbits order (bit i -> byte i/8, bit 7 - i%8, tail zero-padded), then

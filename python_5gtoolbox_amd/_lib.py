@@ -160,6 +160,18 @@ SIGNATURES = {
                                    _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
                                    _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
                                    _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "ldpc5g_transform_precode": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
+                                            _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p]),
+    "ldpc5g_low_papr_seq": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_double, _c.c_int32,
+                                       _c.c_void_p, _c.c_void_p]),
+    "ldpc5g_slot_rx_frontend_tp": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int32,
+                                              _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                              _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_void_p,
+                                              _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "ldpc5g_slot_map_tp": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                      _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                      _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32,
+                                      _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "ldpc5g_pack_records": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                        _c.c_void_p]),

@@ -1,7 +1,8 @@
 // ldpc5g_prbs.h — the parts of the Gold sequence c(n) of py5gphy/common/nrPRBS.py:5-25 (gen_nrPRBS)
 // that ldpc5g_phy.hip (scrambling codes) and ldpc5g_slot.hip (DMRS sequences) share: the constexpr
-// generator of the jump-ahead matrices T^(2^i) and the 32-position step.  Each translation unit
-// builds the device table it needs from the generator (column form there, row form here).
+// generator of the jump-ahead matrices T^(2^i), the 32-position step, and the row-form device
+// table with the wave-wide jump that ldpc5g_slot.hip and ldpc5g_tp.hip (hopping) use.  ldpc5g_phy.hip
+// builds its column-form device table from the generator itself.
 #pragma once
 #include <stdint.h>
 
@@ -42,6 +43,38 @@ __device__ __forceinline__ uint32_t prbs_step32(uint32_t& s, bool x2) {
     W |= (n2 & 0xFull) << 59;                             // x(m+59 .. m+62)
     s = (uint32_t)(W >> 32) & 0x7FFFFFFFu;
     return (uint32_t)W;
+}
+
+// The jump-ahead matrices T^(2^i) in ROW form, r[q][i][b] bit j = bit b of column j:
+// bit b of T^(2^i) s is the parity of s & r[q][i][b], so a wave applies one matrix to a wave-uniform
+// state with one AND, one population count and one ballot, lane b making bit b.  Levels 0..12 reach
+// every position below 8192: the last bit a DMRS sequence can need is 1600 + 2 * 6 * 275 = 4900, and
+// the idle waves of a last workgroup start at most 4 * 255 bits further on.
+constexpr int kDmrsLevels = 13;
+struct PrbsRows {
+    uint32_t r[2][kDmrsLevels][32];
+};
+constexpr PrbsRows make_prbs_rows() {
+    const PrbsTables P = make_prbs_tables();
+    PrbsRows R{};
+    for (int q = 0; q < 2; ++q)
+        for (int i = 0; i < kDmrsLevels; ++i)
+            for (int b = 0; b < 31; ++b)
+                for (int j = 0; j < 31; ++j) R.r[q][i][b] |= ((P.t[q][i][j] >> b) & 1u) << j;
+    return R;
+}
+__device__ const PrbsRows kPrbsRows = make_prbs_rows();
+
+// T^n s for wave-uniform s and n < 2^kDmrsLevels; every lane of the wave must be active.
+__device__ __forceinline__ uint32_t prbs_jump_wave(int q, uint32_t s, uint32_t n) {
+    const int b = threadIdx.x & 31;
+    uint32_t rows[kDmrsLevels];
+#pragma unroll
+    for (int i = 0; i < kDmrsLevels; ++i) rows[i] = kPrbsRows.r[q][i][b];   // all loads in flight at once
+#pragma unroll
+    for (int i = 0; i < kDmrsLevels; ++i)
+        if ((n >> i) & 1u) s = (uint32_t)__ballot(__popc(s & rows[i]) & 1) & 0x7FFFFFFFu;
+    return s;
 }
 
 }  // namespace ldpc5g_impl

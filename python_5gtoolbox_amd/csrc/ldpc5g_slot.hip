@@ -45,38 +45,6 @@ __device__ __forceinline__ uint32_t dmrs_cinit(const SlotDmrs& c, int32_t slot, 
     return (uint32_t)(((a << 17) + (uint64_t)(2 * c.nid + c.nscid)) & 0x7FFFFFFFull);
 }
 
-// The jump-ahead matrices T^(2^i) of ldpc5g_prbs.h in ROW form, r[q][i][b] bit j = bit b of column j:
-// bit b of T^(2^i) s is the parity of s & r[q][i][b], so a wave applies one matrix to a wave-uniform
-// state with one AND, one population count and one ballot, lane b making bit b.  Levels 0..12 reach
-// every position below 8192: the last bit a DMRS sequence can need is 1600 + 2 * 6 * 275 = 4900, and
-// the idle waves of a last workgroup start at most 4 * 255 bits further on.
-constexpr int kDmrsLevels = 13;
-struct PrbsRows {
-    uint32_t r[2][kDmrsLevels][32];
-};
-constexpr PrbsRows make_prbs_rows() {
-    const PrbsTables P = make_prbs_tables();
-    PrbsRows R{};
-    for (int q = 0; q < 2; ++q)
-        for (int i = 0; i < kDmrsLevels; ++i)
-            for (int b = 0; b < 31; ++b)
-                for (int j = 0; j < 31; ++j) R.r[q][i][b] |= ((P.t[q][i][j] >> b) & 1u) << j;
-    return R;
-}
-__device__ const PrbsRows kPrbsRows = make_prbs_rows();
-
-// T^n s for wave-uniform s and n < 2^kDmrsLevels; every lane of the wave must be active.
-__device__ __forceinline__ uint32_t prbs_jump_wave(int q, uint32_t s, uint32_t n) {
-    const int b = threadIdx.x & 31;
-    uint32_t rows[kDmrsLevels];
-#pragma unroll
-    for (int i = 0; i < kDmrsLevels; ++i) rows[i] = kPrbsRows.r[q][i][b];   // all loads in flight at once
-#pragma unroll
-    for (int i = 0; i < kDmrsLevels; ++i)
-        if ((n >> i) & 1u) s = (uint32_t)__ballot(__popc(s & rows[i]) & 1) & 0x7FFFFFFFu;
-    return s;
-}
-
 // The lane's four sequence bits c(bit0 + 4 lane .. + 3), lane = threadIdx.x % 64, of the sequence
 // started by cinit; bit0 is wave-uniform.  Each wave makes its own 256 bits: the jump above, then
 // eight uniform 32-bit steps.  No LDS, no barrier.

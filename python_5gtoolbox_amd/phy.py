@@ -19,6 +19,11 @@ entry points ldpc5g_prbs, ldpc5g_scramble_modulate, ldpc5g_demod_descramble (inc
     slot_map(sym (T, nre*NL), slots, pdsch_config, carrier_prbs, num_ant) -> grid (T, num_ant, 14*carrier_re)
                         (nr_pdsch_dmrs.py:90-120, nr_pdsch_process.py:27-42, nrpdsch_resource_mapping.py:58-85)
     dmrs_symlist(Ld, DMRSAddPos), slot_data_re_idx(pdsch_config) -> (re_idx, usage): host helpers
+    transform_precode(x (T, nsym*12*RBSize), rb_size, inverse=False) -> same shape: the DFT / IDFT of
+        every 12*RBSize block                            (nr_pusch_process.py:39-54, nr_pusch.py:170-194)
+    low_papr_seq(u, v, MZC, alpha=0.0) -> (n, MZC) complex128              (lowPAPR_seq.py:5-41)
+    pusch_tp_frontend / pusch_tp_map: slot_frontend / slot_map for a pusch_config with nTransPrecode = 1
+        (the low-PAPR DMRS with group / sequence hopping, nr_pusch_dmrs.py:216-249)
 mod: a MOD_ID value (the order Qm for QPSK..1024QAM, 1 BPSK, -1 pi/2-BPSK).
 Device tensors in and out; asynchronous on the current stream.
 """
@@ -320,7 +325,8 @@ def _slot_params(config):
         assert dm["dmrs_TypeA_Position"] == "pos2"
         if config["nTransPrecode"] != 0:
             raise NotImplementedError("nTransPrecode != 0: transform precoding (the low-PAPR DMRS sequence, "
-                                      "nr_pusch_dmrs.py:216-228) is not provided")
+                                      "nr_pusch_dmrs.py:216-228) is not provided here: see pusch_tp_frontend, "
+                                      "pusch_tp_map and sch.sch_pusch_tp_rx_batch")
         nid = dm["transformPrecodingDisabled"]["NID0" if nscid == 0 else "NID1"]
     else:
         nid = dm["nNIDnSCID"]
@@ -445,4 +451,203 @@ def slot_map(sym, slots, pdsch_config, carrier_prbs, num_ant, precoding=None, ou
             _lib.ptr(sym), _ld(sym, T, nre * NL), _lib.ptr(re_idx), nre, _lib.ptr(slots), T, W // 14,
             p["rb_start"], p["rb_size"], int(num_ant), NL, pm, S, syms, p["nid"], p["nscid"], p["cdm"],
             _lib.ptr(out), _ld(out, T, int(num_ant) * W), _lib.stream_ptr(dev)))
+    return out
+
+
+# ------------------------------------------------------------------ PUSCH transform precoding
+HOPPING_ID = {"neither": 0, "groupHopping": 1, "sequenceHopping": 2}   # groupOrSequenceHopping -> ABI
+
+
+def tp_rb_ok(rb_size):
+    """RBSize = 2^a 3^b 5^c in 1..275 (38.211 6.3.1.4): the lengths the transform is built for."""
+    n = int(rb_size)
+    if not 1 <= n <= 275:
+        return False
+    for f in (2, 3, 5):
+        while n % f == 0:
+            n //= f
+    return n == 1
+
+
+def _tp_check_rb(rb_size):
+    if not tp_rb_ok(rb_size):
+        raise NotImplementedError(f"RBSize {rb_size}: transform precoding needs RBSize = 2^a 3^b 5^c in 1..275 "
+                                  "(38.211 6.3.1.4)")
+
+
+def transform_precode(x, rb_size, inverse=False, out=None):
+    """The transform precoding of 38.211 6.3.1.4 and its inverse (ldpc5g_transform_precode): every
+    block of M = 12*rb_size elements of a row of x is replaced by its orthonormal DFT
+    (np.fft.fft(.) / sqrt(M), nr_pusch_process.py:53) or, with inverse=True, IDFT (np.fft.ifft(.) *
+    sqrt(M), nr_pusch.py:188).  x: (T, nsym*M) complex64 / complex128 device tensor (only the row
+    stride is free), nsym <= 14; float64 arithmetic for both.  Returns a new tensor or fills out,
+    which may be x itself."""
+    _tp_check_rb(rb_size)
+    t = _lib.require_gpu()
+    M = 12 * int(rb_size)
+    assert x.dim() == 2 and x.dtype in (t.complex64, t.complex128) and x.stride(1) == 1, \
+        "x: (T, nsym*12*rb_size) complex, only the row stride is free"
+    T, W = x.shape
+    assert W % M == 0 and 1 <= W // M <= 14, f"rows of {W} elements are not 1..14 blocks of 12*rb_size = {M}"
+    if out is None:
+        out = t.empty((T, W), dtype=x.dtype, device=x.device)
+    assert out.dtype == x.dtype and out.shape == (T, W) and out.stride(1) == 1 and out.device == x.device
+    with t.cuda.device(x.device):
+        _lib.check(_lib.lib().ldpc5g_transform_precode(
+            _lib.ptr(x), _ld(x, T, W), _lib.ptr(out), _ld(out, T, W),
+            _lib.F32 if x.dtype == t.complex64 else _lib.F64, T, W // M, int(rb_size), 1 if inverse else 0,
+            _lib.stream_ptr(x.device)))
+    return out
+
+
+def low_papr_seq(u, v, MZC, alpha=0.0, device=None):
+    """Low-PAPR sequences exp(j alpha m) rbar_{u,v}(m), m < MZC (ldpc5g_low_papr_seq;
+    gen_lowPAPR_seq, lowPAPR_seq.py:5-41).  u, v: integers or sequences of n integers (group 0..29,
+    base sequence 0..1, 0 when MZC < 72 — checked as the reference asserts), or (n,) int32 device
+    tensors (not checked).  Returns an (n, MZC) complex128 device tensor.  MZC in {6, 12, 18, 24}
+    are the tables of 38.211 5.2.2.2, which are not provided."""
+    import numpy as np
+    MZC = int(MZC)
+    assert MZC % 6 == 0 and 6 <= MZC <= 3300, f"MZC {MZC}: a multiple of 6 in 6..3300"
+    if MZC in (6, 12, 18, 24):
+        raise NotImplementedError(f"MZC {MZC}: the sequences of length 6, 12, 18, 24 are the tables of 38.211 "
+                                  "5.2.2.2, which are not provided")
+    host = not hasattr(u, "data_ptr")
+    if host:
+        u = np.atleast_1d(np.asarray(u)).astype(np.int32)
+        v = np.broadcast_to(np.atleast_1d(np.asarray(v)).astype(np.int32), u.shape).copy()
+        assert u.ndim == 1 and u.size >= 1
+        assert ((u >= 0) & (u < 30)).all(), "u in range(30)"
+        assert ((v >= 0) & (v <= (1 if MZC >= 72 else 0))).all(), "v == 0 for MZC <= 60, v in [0, 1] for MZC >= 72"
+    t = _lib.require_gpu()
+    if host:
+        dev = t.device("cuda", t.cuda.current_device()) if device is None else t.device(device)
+        u, v = t.from_numpy(u).to(dev), t.from_numpy(v).to(dev)
+    assert u.dim() == 1 and u.dtype == t.int32 and u.is_contiguous()
+    assert v.shape == u.shape and v.dtype == t.int32 and v.is_contiguous() and v.device == u.device
+    n = u.shape[0]
+    out = t.empty((n, MZC), dtype=t.complex128, device=u.device)
+    with t.cuda.device(u.device):
+        _lib.check(_lib.lib().ldpc5g_low_papr_seq(_lib.ptr(u), _lib.ptr(v), n, float(alpha), MZC, _lib.ptr(out),
+                                                  _lib.stream_ptr(u.device)))
+    return out
+
+
+def _tp_params(config, base_seq=None, need_seq=True):
+    """_slot_params for a pusch_config with nTransPrecode = 1: the reference's asserts
+    (nr_pusch_dmrs.py:127-145, nr_pusch_process.py:45, nr_pusch.py:176-179) and this library's
+    refusals."""
+    assert "nTransPrecode" in config, "a pusch_config is wanted"
+    assert config["nTransPrecode"] == 1, f"nTransPrecode {config['nTransPrecode']}: 1 wanted (0: slot_frontend / slot_map)"
+    p = _slot_params(dict(config, nTransPrecode=0))
+    assert p["NL"] == 1, f"num_of_layers {p['NL']}: transform precoding has one layer (nr_pusch_process.py:45)"
+    assert p["cdm"] == 2, ("NumCDMGroupsWithoutData 1: data on the DMRS symbols breaks the reference's "
+                           "assert demod_LLRs.size % MPUSCHSC == 0 (nr_pusch.py:179)")
+    _tp_check_rb(p["rb_size"])
+    en = config["DMRS"]["transformPrecodingEnabled"]
+    nid = int(en["nPuschID"])
+    assert 0 <= nid <= 1007, f"nPuschID {nid} outside 0..1007"
+    hop = en["groupOrSequenceHopping"]
+    assert hop in HOPPING_ID, f"groupOrSequenceHopping {hop!r}: one of {sorted(HOPPING_ID)}"
+    if need_seq and p["rb_size"] <= 4 and base_seq is None:
+        raise NotImplementedError(f"RBSize <= 4 (RBSize {p['rb_size']}): the DMRS sequences of length 6..24 are the "
+                                  "tables of 38.211 5.2.2.2, which are not provided: pass them as base_seq")
+    return dict(p, npuschid=nid, hopping=HOPPING_ID[hop])
+
+
+def pusch_tp_data_re_idx(pusch_config):
+    """slot_data_re_idx for a pusch_config with nTransPrecode = 1 (the RE usage does not depend on
+    the DMRS sequence)."""
+    _tp_params(pusch_config, need_seq=False)
+    return slot_data_re_idx(dict(pusch_config, nTransPrecode=0))
+
+
+def _tp_base_seq(base_seq, T, S, MZC, dev):
+    """base_seq as a (T, S, MZC) complex128 contiguous device tensor; an array (S, MZC) or
+    (T, S, MZC) on the host is uploaded."""
+    import numpy as np
+    t = _lib.torch()
+    if base_seq is None:
+        return None
+    if not hasattr(base_seq, "data_ptr"):
+        a = np.asarray(base_seq, np.complex128)
+        assert a.shape in ((S, MZC), (T, S, MZC)), f"base_seq {a.shape}: ({S}, {MZC}) or ({T}, {S}, {MZC}) wanted"
+        base_seq = t.from_numpy(np.array(np.broadcast_to(a, (T, S, MZC)))).to(dev)   # a writable copy
+    assert base_seq.dtype == t.complex128 and base_seq.shape == (T, S, MZC) and base_seq.is_contiguous() \
+        and base_seq.device == dev, f"base_seq: ({T}, {S}, {MZC}) complex128 contiguous on {dev}"
+    return base_seq
+
+
+def pusch_tp_frontend(grid, slots, pusch_config, want=("h_ls", "y"), base_seq=None):
+    """slot_frontend for a pusch_config with nTransPrecode = 1 (ldpc5g_slot_rx_frontend_tp;
+    pusch_dmrs_LS_est, nr_pusch_dmrs.py:107-200 with the low-PAPR sequence of :216-249, its group /
+    sequence hopping following slots).  One layer, NumCDMGroupsWithoutData = 2, RBSize = 2^a 3^b 5^c.
+    base_seq: the DMRS base sequences, (S, 6*RBSize) or (T, S, 6*RBSize) complex128 (host array or
+    device tensor), instead of the generated ones; needed for RBSize <= 4.  Returns, in the order of
+    `want`, h_ls (T, S, 3*RBSize, Nr, 1) and y (T, 14*12*RBSize, Nr) of grid's dtype."""
+    assert want and all(w in ("h_ls", "y") for w in want), f"want {want!r}: a selection of 'h_ls', 'y'"
+    p = _tp_params(pusch_config, base_seq)   # asserts and refusals come before any GPU work
+    t = _lib.require_gpu()
+    assert grid.dim() == 3 and grid.dtype in (t.complex64, t.complex128) and grid[0].is_contiguous(), \
+        "grid: (T, Nr, 14*carrier_re) complex, only the slot stride is free"
+    T, Nr, W = grid.shape
+    assert W % 14 == 0, f"grid rows of {W} elements are not 14 symbols"
+    assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == grid.device
+    S, N = len(p["symlist"]), 3 * p["rb_size"]
+    dev = grid.device
+    bs = _tp_base_seq(base_seq, T, S, 2 * N, dev)
+    h_ls = t.empty((T, S, N, Nr, 1), dtype=grid.dtype, device=dev) if "h_ls" in want else None
+    y = t.empty((T, 14 * 4 * N, Nr), dtype=grid.dtype, device=dev) if "y" in want else None
+    syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
+    with t.cuda.device(dev):
+        _lib.check(_lib.lib().ldpc5g_slot_rx_frontend_tp(
+            _lib.ptr(grid), _ld(grid, T, Nr * W), _lib.F32 if grid.dtype == t.complex64 else _lib.F64,
+            _lib.ptr(slots), T, W // 14, p["rb_start"], p["rb_size"], Nr, p["ports"][0] - 1000, S, syms,
+            p["npuschid"], p["hopping"], _lib.ptr(bs) if bs is not None else None,
+            _lib.ptr(h_ls) if h_ls is not None else None, S * N * Nr,
+            _lib.ptr(y) if y is not None else None, 14 * 4 * N * Nr, _lib.stream_ptr(dev)))
+    outs = {"h_ls": h_ls, "y": y}
+    return tuple(outs[w] for w in want)
+
+
+def pusch_tp_map(sym, slots, pusch_config, carrier_prbs, num_ant, precoding=None, out=None, re_idx=None,
+                 base_seq=None):
+    """slot_map for a pusch_config with nTransPrecode = 1: transform_precode on the modulated
+    symbols (nr_pusch_process.py:39-54), then ldpc5g_slot_map_tp — the low-PAPR DMRS of
+    nr_pusch_dmrs.py:66-101, the precoding and the data RE mapping.  sym: (T, nre) complex64
+    modulated symbols of the one layer, nre = len(pusch_tp_data_re_idx(pusch_config)[0]) — whole
+    symbols of 12*RBSize; precoding: (num_ant, 1) array-like or None (antenna 0 carries the layer);
+    the layer's port is PortIndexList[0]; base_seq as pusch_tp_frontend.  Returns the grid
+    (T, num_ant, 14*12*carrier_prbs) complex64 (out, or a new zeroed one)."""
+    import numpy as np
+    p = _tp_params(pusch_config, base_seq)
+    t = _lib.require_gpu()
+    dev = sym.device
+    if re_idx is None:
+        re_idx = t.from_numpy(pusch_tp_data_re_idx(pusch_config)[0]).to(dev)
+    assert re_idx.dim() == 1 and re_idx.dtype == t.int32 and re_idx.is_contiguous() and re_idx.device == dev
+    nre = re_idx.shape[0]
+    assert sym.dim() == 2 and sym.dtype == t.complex64 and sym.stride(1) == 1
+    T = sym.shape[0]
+    assert sym.shape[1] == nre, f"sym has {sym.shape[1]} symbols per slot, the allocation holds nre = {nre}"
+    assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == dev
+    W = 14 * 12 * int(carrier_prbs)
+    if out is None:
+        out = t.zeros((T, int(num_ant), W), dtype=t.complex64, device=dev)
+    assert out.dtype == t.complex64 and out.shape == (T, int(num_ant), W) and out[0].is_contiguous() and out.device == dev
+    pm = None
+    if precoding is not None:
+        w = np.ascontiguousarray(np.asarray(precoding, np.complex64).reshape(-1, 1)[:int(num_ant)])
+        assert w.shape == (int(num_ant), 1), f"precoding {w.shape}: (num_ant, 1) wanted"
+        pm = w.view(np.float32).ctypes.data_as(_lib.ctypes.c_void_p)
+    S, N = len(p["symlist"]), 3 * p["rb_size"]
+    bs = _tp_base_seq(base_seq, T, S, 2 * N, dev)
+    spread = transform_precode(sym, p["rb_size"])
+    syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
+    with t.cuda.device(dev):
+        _lib.check(_lib.lib().ldpc5g_slot_map_tp(
+            _lib.ptr(spread), _ld(spread, T, nre), _lib.ptr(re_idx), nre, _lib.ptr(slots), T, W // 14,
+            p["rb_start"], p["rb_size"], int(num_ant), p["ports"][0] - 1000, pm, S, syms, p["npuschid"],
+            p["hopping"], _lib.ptr(bs) if bs is not None else None, _lib.ptr(out), _ld(out, T, int(num_ant) * W),
+            _lib.stream_ptr(dev)))
     return out

@@ -452,6 +452,36 @@ def sch_slot_rx_batch(grid, slots, pdsch_config, ce, algo, mod, cfg, L, re_idx=N
     return sch_ml_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, **kw)
 
 
+def sch_pusch_tp_rx_batch(grid, slots, pusch_config, ce, algo, mod, cfg, L, re_idx=None, base_seq=None, **kw):
+    """sch_slot_rx_batch for a pusch_config with nTransPrecode = 1 (NrPUSCH.H_LS_est,
+    NrChannelEstimation.channel_est and NrPUSCH.RX_process with its de-spreading branch,
+    nr_pusch.py:116-219): phy.pusch_tp_frontend, the channel estimator, phy.equalize,
+    phy.transform_precode(inverse=True) on the equalised symbols of every data symbol (:184-191) and
+    sch_rx_batch, all on the device and on the current stream.  The noise variances go to the
+    demodulator unchanged, per RE, as nr_pusch.py:190 has them.  algo: "ZF", "ZF-IRC", "MMSE" or
+    "MMSE-IRC"; the ML names are refused, the reference discards their LLRs on this branch (:178).
+    re_idx: the device tensor of phy.pusch_tp_data_re_idx(pusch_config)[0] (uploaded here when not
+    given); base_seq as phy.pusch_tp_frontend; everything else as sch_slot_rx_batch."""
+    from . import phy
+    if algo in _lib.ML_ALGO:
+        raise NotImplementedError(f"algo {algo!r}: with transform precoding the reference demodulates after the "
+                                  "de-spreading IDFT and throws the ML detectors' LLRs away (nr_pusch.py:178-194); "
+                                  f"use one of {sorted(_lib.EQ_ALGO)}")
+    assert algo in _lib.EQ_ALGO, f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO)}"
+    p = phy._tp_params(pusch_config, base_seq)   # asserts and refusals come before any GPU work
+    h_ls, y = phy.pusch_tp_frontend(grid, slots, pusch_config, base_seq=base_seq)
+    t = _lib.torch()
+    if re_idx is None:
+        re_idx = t.from_numpy(phy.pusch_tp_data_re_idx(pusch_config)[0]).to(grid.device)
+    nre = re_idx.shape[0]
+    assert nre * phy.bits_per_symbol(mod) == cfg.G, f"nre*Qm = {nre}*{phy.bits_per_symbol(mod)} != G = {cfg.G}"
+    ce = dict(ce, sym_map=p["symlist"], num_cdm_groups=p["cdm"])
+    y, h, cov = _ce_stage(y, h_ls, ce)
+    sym, nv = phy.equalize(y, h, cov, algo, re_idx)
+    phy.transform_precode(sym, p["rb_size"], inverse=True, out=sym)
+    return sch_rx_batch(sym, nv, mod, cfg, L, **kw)
+
+
 # ------------------------------------------------------------ per-TB configurations (multi)
 SchMultiResult = namedtuple(
     "SchMultiResult", "tb_ok tbblk llr_dn ck status iters cb_crc_ok tb_rem rows")
