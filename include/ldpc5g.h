@@ -703,6 +703,45 @@ int ldpc5g_slot_map_tp(const void* sym, int64_t ldsym, const int32_t* re_idx, in
                        const float* precoding, int32_t S, const int32_t* sym_idx, int32_t nPuschID, int32_t hopping,
                        const void* base_seq, void* grid, int64_t ldgrid, void* stream);
 
+/* ================================================ OFDM low-PHY: time-domain slot <-> resource grid
+ * Rx_low_phy (nr_lowphy/rx_lowphy_process.py:35-98) and Tx_low_phy (tx_lowphy_process.py:10-80),
+ * batched over T slots and Nr (num_ant) antennas, one launch each.  td holds slots of 15 nfft
+ * samples (14 symbols, each its cyclic prefix then nfft samples), sample n of antenna r of slot t at
+ * td[t * ld_td_slot + r * ld_td_ant + n]; grid holds RE k of symbol s at grid[t * ld_g_slot +
+ * r * ld_g_ant + s * carrier_re + k].  All four strides are free, in COMPLEX elements: the slot
+ * front end's [t][r][.] and the reference's waveform layout [r][slot * 15 nfft + n] are the same
+ * call.  CP lengths are the reference's 4096-point lists divided by 4096 / nfft: [352] + [288]*13
+ * (scs 30), [320] + [288]*6 + [320] + [288]*6 (scs 15).  dtype LDPC5G_F32 (complex64) or LDPC5G_F64
+ * (complex128) is the storage type of td and grid; the arithmetic is float64 for both and the
+ * complex64 result is the complex128 one rounded.  Asynchronous on `stream`, no allocation, no
+ * synchronisation, no atomics; bit-identical from run to run, a batch equals its slots one by one.
+ * td and grid must not overlap.  The antennas are never permuted (the reference's fftshift without
+ * axes also rolls them; that belongs to the Python drop-ins).
+ *
+ * ldpc5g_ofdm_demod, symbol s with off samples before it, cp its prefix, h = cp_short / 2: the
+ * nfft samples from off + cp - h on, times exp(+2 pi j carrier_hz (off + cp) / fs), fs = nfft scs
+ * 1000 (skipped when carrier_hz is a multiple of fs; the phase is the exact rational (carrier_hz
+ * (off + cp) mod fs) / fs); forward FFT / sqrt(nfft); fftshift; position i of the shifted array
+ * times exp(2 pi j h i / nfft); positions (nfft - carrier_re) / 2 ... go to the grid.
+ *
+ * ldpc5g_ofdm_mod, the inverse: the carrier_re REs at the centre of a zeroed nfft array — with dm
+ * (DEVICE float64 [T][14], or NULL) RE k first times exp(2 pi j k scs 1000 dm[t][s]), that product
+ * rounded to the storage type — ifftshift, inverse FFT * sqrt(nfft), then cp + nfft samples
+ * td[n] = x[(n - cp) mod nfft] times exp(-2 pi j carrier_hz (off + cp) / fs).  The grid is not
+ * written.
+ *
+ * Limits, checked on the host BEFORE any HIP call (LDPC5G_ESIZE and a message naming the
+ * argument): a known dtype; T in 1..65535; Nr / num_ant in {1, 2, 4}; nfft in {128, 256, 512, 1024,
+ * 2048, 4096}; carrier_re a multiple of 12 in 12..nfft; scs in {15, 30}; ld_td_slot (T > 1) and
+ * ld_td_ant (Nr > 1) at least 15 nfft, ld_g_slot and ld_g_ant at least 14 carrier_re; td, grid
+ * non-null; td, grid, dm aligned to their element. */
+int ldpc5g_ofdm_demod(const void* td, int64_t ld_td_slot, int64_t ld_td_ant, void* grid, int64_t ld_g_slot,
+                      int64_t ld_g_ant, int32_t dtype, int32_t T, int32_t Nr, int32_t nfft, int32_t carrier_re,
+                      int32_t scs, int64_t carrier_hz, void* stream);
+int ldpc5g_ofdm_mod(const void* grid, int64_t ld_g_slot, int64_t ld_g_ant, const double* dm, void* td,
+                    int64_t ld_td_slot, int64_t ld_td_ant, int32_t dtype, int32_t T, int32_t num_ant, int32_t nfft,
+                    int32_t carrier_re, int32_t scs, int64_t carrier_hz, void* stream);
+
 /* ================================================ gather records (multi-GPU)
  * Record r (a row of rec, stride ldr bytes) = the nbits int8 bits of row r of `bits` (values 0/1)
  * packed in np.packbits order (bit i -> byte i/8, bit 7 - i%8, tail zero-padded), then

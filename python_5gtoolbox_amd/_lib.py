@@ -172,6 +172,12 @@ SIGNATURES = {
                                       _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
                                       _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32,
                                       _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "ldpc5g_ofdm_demod": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int64,
+                                     _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                     _c.c_int64, _c.c_void_p]),
+    "ldpc5g_ofdm_mod": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64,
+                                   _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                   _c.c_int32, _c.c_int64, _c.c_void_p]),
     "ldpc5g_pack_records": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                        _c.c_void_p]),

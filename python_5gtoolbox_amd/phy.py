@@ -24,6 +24,10 @@ entry points ldpc5g_prbs, ldpc5g_scramble_modulate, ldpc5g_demod_descramble (inc
     low_papr_seq(u, v, MZC, alpha=0.0) -> (n, MZC) complex128              (lowPAPR_seq.py:5-41)
     pusch_tp_frontend / pusch_tp_map: slot_frontend / slot_map for a pusch_config with nTransPrecode = 1
         (the low-PAPR DMRS with group / sequence hopping, nr_pusch_dmrs.py:216-249)
+    ofdm_params(scs, carrier_prbs) -> (nfft, cp_list, slot_len)
+    ofdm_demod(td (T, Nr, 15*nfft), scs, carrier_prbs, carrier_frequency_in_mhz=0) -> grid (T, Nr, 14*12*prbs)
+    ofdm_mod(grid, scs, carrier_prbs, carrier_frequency_in_mhz=0, dm=None) -> td   (nr_lowphy/rx_lowphy_process.py:35-98,
+                                                                                   tx_lowphy_process.py:10-80)
 mod: a MOD_ID value (the order Qm for QPSK..1024QAM, 1 BPSK, -1 pi/2-BPSK).
 Device tensors in and out; asynchronous on the current stream.
 """
@@ -650,4 +654,101 @@ def pusch_tp_map(sym, slots, pusch_config, carrier_prbs, num_ant, precoding=None
             p["rb_start"], p["rb_size"], int(num_ant), p["ports"][0] - 1000, pm, S, syms, p["npuschid"],
             p["hopping"], _lib.ptr(bs) if bs is not None else None, _lib.ptr(out), _ld(out, T, int(num_ant) * W),
             _lib.stream_ptr(dev)))
+    return out
+
+
+# ------------------------------------------------------------------ OFDM low-PHY
+OFDM_NFFT = (128, 256, 512, 1024, 2048, 4096)   # Rx_low_phy's assert (rx_lowphy_process.py:57)
+_CP4096 = {30: [352] + [288] * 13, 15: [320] + [288] * 6 + [320] + [288] * 6}
+
+
+def ofdm_params(scs, carrier_prbs):
+    """(nfft, cp_list, slot_len) of a carrier: nfft = 2**ceil(log2(12*prbs/0.85)) (get_FFT_IFFT_size,
+    nr_slot.py:64-69), the 14 cyclic-prefix lengths — the reference's 4096-point lists divided by
+    4096/nfft (rx_lowphy_process.py:60-69) — and the slot length sum(cp) + 14*nfft = 15*nfft samples.
+    Raises NotImplementedError for a subcarrier spacing other than 15 / 30 kHz or an nfft outside
+    128..4096."""
+    scs, prbs = int(scs), int(carrier_prbs)
+    if scs not in _CP4096:
+        raise NotImplementedError(f"scs {scs}: the low-PHY's CP tables are those of 15 and 30 kHz")
+    assert prbs >= 1, f"carrier_prbs {carrier_prbs}"
+    nfft = 1
+    while 17 * nfft < 240 * prbs:   # nfft >= 12 prbs / 0.85, in integers
+        nfft *= 2
+    if nfft not in OFDM_NFFT:
+        raise NotImplementedError(f"carrier_prbs {prbs}: nfft {nfft} outside {OFDM_NFFT}")
+    cp = [c * nfft // 4096 for c in _CP4096[scs]]
+    return nfft, cp, sum(cp) + 14 * nfft
+
+
+def _carrier_hz(carrier_frequency_in_mhz):
+    return int(carrier_frequency_in_mhz * (10 ** 6))   # rx_lowphy_process.py:49
+
+
+def _ofdm_check(t, x, name, W, other):
+    assert x.dim() == 3 and x.dtype in (t.complex64, t.complex128) and x.shape[2] == W and x.stride(2) == 1, \
+        f"{name}: (T, Nr, {W}) complex64 / complex128, strides free on the first two dimensions"
+    assert x.shape[1] in (1, 2, 4), f"{name}: {x.shape[1]} antennas, 1, 2 or 4 supported"
+    if other is not None:
+        assert other.dtype == x.dtype and other.device == x.device and other.shape[:2] == x.shape[:2], \
+            f"out: dtype, device and (T, Nr) of {name}"
+
+
+def _st(x, d, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
+    return x.stride(d) if x.shape[d] > 1 else row
+
+
+def ofdm_demod(td, scs, carrier_prbs, carrier_frequency_in_mhz=0, out=None):
+    """Rx_low_phy (rx_lowphy_process.py:35-98) for T slots x Nr antennas in one launch
+    (ldpc5g_ofdm_demod): the per-symbol carrier phase correction, the half-CP window, the FFT, the
+    half-CP ramp and the crop to the carrier.  td: (T, Nr, 15*nfft) complex64 / complex128 device
+    tensor, any strides on the first two dimensions (a transposed unflatten view of a multi-slot
+    waveform works without a copy).  Returns the grid (T, Nr, 14*12*carrier_prbs) of td's dtype —
+    sch_slot_rx_batch's input — or fills out.  float64 arithmetic for both dtypes.  Antennas are
+    never permuted (the reference's fftshift without axes rolls them: rx_lowphy_process.Rx_low_phy
+    here reproduces that)."""
+    nfft, _, S = ofdm_params(scs, carrier_prbs)
+    hz = _carrier_hz(carrier_frequency_in_mhz)
+    t = _lib.require_gpu()
+    W = 14 * 12 * int(carrier_prbs)
+    _ofdm_check(t, td, "td", S, None)
+    T, Nr = td.shape[:2]
+    if out is None:
+        out = t.empty((T, Nr, W), dtype=td.dtype, device=td.device)
+    _ofdm_check(t, out, "out", W, td)
+    with t.cuda.device(td.device):
+        _lib.check(_lib.lib().ldpc5g_ofdm_demod(
+            _lib.ptr(td), _st(td, 0, S), _st(td, 1, S), _lib.ptr(out), _st(out, 0, W), _st(out, 1, W),
+            _lib.F32 if td.dtype == t.complex64 else _lib.F64, T, Nr, nfft, W // 14, int(scs), hz,
+            _lib.stream_ptr(td.device)))
+    return out
+
+
+def ofdm_mod(grid, scs, carrier_prbs, carrier_frequency_in_mhz=0, dm=None, out=None):
+    """Tx_low_phy (tx_lowphy_process.py:10-80) for T slots x num_ant antennas in one launch
+    (ldpc5g_ofdm_mod): the IFFT, the cyclic prefix and the per-symbol carrier phase compensation of
+    38.211 5.4.  grid: (T, num_ant, 14*12*carrier_prbs) complex64 / complex128 device tensor, any
+    strides on the first two dimensions; dm: None or the per-symbol timing errors in seconds, (T, 14)
+    or (14,) — RE k of symbol s is first turned by exp(2 pi j k scs 1000 dm[t][s]), the product rounded
+    to grid's dtype (:54-55); grid itself is not written.  Returns td (T, num_ant, 15*nfft) of grid's
+    dtype or fills out."""
+    nfft, _, S = ofdm_params(scs, carrier_prbs)
+    hz = _carrier_hz(carrier_frequency_in_mhz)
+    t = _lib.require_gpu()
+    W = 14 * 12 * int(carrier_prbs)
+    _ofdm_check(t, grid, "grid", W, None)
+    T, Na = grid.shape[:2]
+    if dm is not None:
+        dm = t.as_tensor(dm, dtype=t.float64, device=grid.device)
+        assert dm.shape in ((14,), (T, 14)), f"dm {tuple(dm.shape)}: (14,) or (T, 14) seconds per symbol"
+        dm = dm.expand(T, 14).contiguous()
+    if out is None:
+        out = t.empty((T, Na, S), dtype=grid.dtype, device=grid.device)
+    _ofdm_check(t, out, "out", S, grid)
+    with t.cuda.device(grid.device):
+        _lib.check(_lib.lib().ldpc5g_ofdm_mod(
+            _lib.ptr(grid), _st(grid, 0, W), _st(grid, 1, W), _lib.ptr(dm) if dm is not None else None,
+            _lib.ptr(out), _st(out, 0, S), _st(out, 1, S),
+            _lib.F32 if grid.dtype == t.complex64 else _lib.F64, T, Na, nfft, W // 14, int(scs), hz,
+            _lib.stream_ptr(grid.device)))
     return out

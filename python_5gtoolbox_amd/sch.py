@@ -482,6 +482,33 @@ def sch_pusch_tp_rx_batch(grid, slots, pusch_config, ce, algo, mod, cfg, L, re_i
     return sch_rx_batch(sym, nv, mod, cfg, L, **kw)
 
 
+def sch_td_rx_batch(td, slots, config, carrier, ce, algo, mod, cfg, L, **kw):
+    """The reference's receiver from time-domain samples to the transport block for T slots:
+    Rx_low_phy (rx_lowphy_process.py:35-98) by phy.ofdm_demod, then sch_slot_rx_batch — or, when
+    config["nTransPrecode"] == 1, sch_pusch_tp_rx_batch — all on the device and on the current
+    stream, with no host round trip.  td: (T, Nr, 15*nfft) complex64 / complex128 device tensor, any
+    strides on the first two dimensions; carrier: the reference's carrier_config (its "scs", "BW" and
+    "carrier_frequency_in_mhz" are read); config: the pdsch_config or pusch_config; everything else,
+    the keyword arguments included, as the chain's that runs.  Antennas keep their order (the
+    reference's Rx_low_phy rolls them, which no receiver here depends on)."""
+    from . import nr_slot, phy
+    scs = carrier["scs"]
+    prbs = nr_slot.get_carrier_prb_size(scs, carrier["BW"])
+    tp = config.get("nTransPrecode", 0) == 1
+    # the chain's own refusals come before any GPU work
+    if tp:
+        if algo in _lib.ML_ALGO:
+            raise NotImplementedError(f"algo {algo!r}: refused with transform precoding, use one of {sorted(_lib.EQ_ALGO)}")
+        phy._tp_params(config, kw.get("base_seq"))
+    else:
+        assert algo in _lib.EQ_ALGO or algo in _lib.ML_ALGO, \
+            f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO) + sorted(_lib.ML_ALGO)}"
+        phy._slot_params(config)
+    grid = phy.ofdm_demod(td, scs, prbs, carrier.get("carrier_frequency_in_mhz", 0))
+    chain = sch_pusch_tp_rx_batch if tp else sch_slot_rx_batch
+    return chain(grid, slots, config, ce, algo, mod, cfg, L, **kw)
+
+
 # ------------------------------------------------------------ per-TB configurations (multi)
 SchMultiResult = namedtuple(
     "SchMultiResult", "tb_ok tbblk llr_dn ck status iters cb_crc_ok tb_rem rows")
