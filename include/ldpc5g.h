@@ -742,6 +742,55 @@ int ldpc5g_ofdm_mod(const void* grid, int64_t ld_g_slot, int64_t ld_g_ant, const
                     int64_t ld_td_slot, int64_t ld_td_ant, int32_t dtype, int32_t T, int32_t num_ant, int32_t nfft,
                     int32_t carrier_re, int32_t scs, int64_t carrier_hz, void* stream);
 
+/* ================================================ polar code (TS 38.212 §5.3.1, §5.4.1)
+ * The reference's py5gphy/polar, batched: B blocks per launch, bits int8, LLRs float64.
+ *
+ * ldpc5g_polar_plan is host-only.  For one (K, E, nMax, iIL, CRCLEN, padCRC, rnti) — K counts the
+ * CRC — it builds what the kernels need (polar_construct.construct and §5.3.1.2 / §5.4.1.1): N,
+ * the frozen mask F, qPC with nPC and nPCwm (row weight 2^popcount), the u -> ck map, the input
+ * interleaver and its inverse, the PC parity masks, for iIL = 1 the 24 distributed-CRC parity masks
+ * (over u positions) and the 24-bit CRC mask, and the channel interleaver of E.  It returns the
+ * plan's size in bytes (plan == NULL: size only) or a negative error.  The plan is an opaque blob
+ * with a magic number and a version; the caller keeps the host copy and uploads one device copy,
+ * and every entry point below takes both (plan_dev, plan_host) and checks the host copy's magic
+ * and version.  Its first 18 int32: magic, version, bytes, K, E, nMax, iIL, CRCLEN, padCRC, rnti,
+ * N, n, nPC, nPCwm, qPC[3], mode (0 repetition, 1 puncturing, 2 shortening); F (N bytes) follows
+ * at byte offset int32[19].
+ *
+ * Limits, all checked on the host BEFORE any HIP call (LDPC5G_ESIZE and a ldpc5g_last_error()
+ * message): (nMax, iIL, CRCLEN) in {(9, 1, 24), (10, 0, 6), (10, 0, 11)}; E in 1..8192; K > CRCLEN;
+ * for nMax = 10, K in 18..25 or > 30; for iIL = 1, K <= 164; K + nPC <= E and <= N; padCRC in
+ * {0, 1}; rnti in 0..2^24-1; B in 1..2^22; row strides at least their rows (K, N or E); non-null
+ * buffers; a plan with the right magic and version; for decode, algo SC or SCL, L in 1..32 and N in
+ * 32..1024.
+ *
+ *   encode        bits [B][ldb] (K used) -> out [B][ldo] (N): interleave (iIL), PC bits, x = u G_N
+ *   rate_match    d [B][ldi] (N) -> f [B][ldo] (E): sub-block interleaver, bit selection, and with
+ *                 iBIL the triangular channel interleaver
+ *   rate_recover  llr [B][ldi] (E) -> out [B][ldo] (N): repetitions summed whole copies first, then
+ *                 the remainder, sequential float64 adds; punctured positions 0; shortened positions
+ *                 llr_limit.  reference_repetition = 1 reproduces nr_polar_raterecover.py:40, which
+ *                 with iBIL = 1 sums the LLRs it did not de-interleave.
+ *   decode        llr [B][ldl] (N) -> ck [B][ldc] (K), status [B] (1 decoded, 0 failed: that ck row
+ *                 is all -1), pm [B] (the returned path's metric; +inf on failure).  SC ignores L
+ *                 and always reports 1.  N = 1024 with L > 16 keeps its largest one or two LLR layers in a
+ *                 stream-ordered allocation (hipMallocAsync / hipFreeAsync on `stream`), at most
+ *                 1024 workgroups' worth; every other shape runs from LDS alone. */
+#define LDPC5G_POLAR_SC 0
+#define LDPC5G_POLAR_SCL 1
+int64_t ldpc5g_polar_plan(int32_t K, int32_t E, int32_t nMax, int32_t iIL, int32_t crclen, int32_t padCRC,
+                          int32_t rnti, void* plan, int64_t plan_bytes);
+int ldpc5g_polar_encode(const void* plan_dev, const void* plan_host, const int8_t* bits, int64_t ldb, int8_t* out,
+                        int64_t ldo, int32_t B, void* stream);
+int ldpc5g_polar_rate_match(const void* plan_dev, const void* plan_host, const int8_t* d, int64_t ldi, int8_t* f,
+                            int64_t ldo, int32_t B, int32_t iBIL, void* stream);
+int ldpc5g_polar_rate_recover(const void* plan_dev, const void* plan_host, const double* llr, int64_t ldi,
+                              double* out, int64_t ldo, int32_t B, int32_t iBIL, double llr_limit,
+                              int32_t reference_repetition, void* stream);
+int ldpc5g_polar_decode(const void* plan_dev, const void* plan_host, const double* llr, int64_t ldl, int8_t* ck,
+                        int64_t ldc, uint8_t* status, double* pm, int32_t B, int32_t algo, int32_t L,
+                        void* stream);
+
 /* ================================================ gather records (multi-GPU)
  * Record r (a row of rec, stride ldr bytes) = the nbits int8 bits of row r of `bits` (values 0/1)
  * packed in np.packbits order (bit i -> byte i/8, bit 7 - i%8, tail zero-padded), then

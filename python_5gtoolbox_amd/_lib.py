@@ -178,6 +178,17 @@ SIGNATURES = {
     "ldpc5g_ofdm_mod": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                    _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
                                    _c.c_int32, _c.c_int64, _c.c_void_p]),
+    "ldpc5g_polar_plan": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                       _c.c_int32, _c.c_void_p, _c.c_int64]),
+    "ldpc5g_polar_encode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
+                                       _c.c_int32, _c.c_void_p]),
+    "ldpc5g_polar_rate_match": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                           _c.c_int64, _c.c_int32, _c.c_int32, _c.c_void_p]),
+    "ldpc5g_polar_rate_recover": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                             _c.c_int64, _c.c_int32, _c.c_int32, _c.c_double, _c.c_int32,
+                                             _c.c_void_p]),
+    "ldpc5g_polar_decode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
+                                       _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p]),
     "ldpc5g_pack_records": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                        _c.c_void_p]),

@@ -1,0 +1,358 @@
+"""float64 numpy restatement of the polar codec (TS 38.212 §5.3.1, §5.4.1) and of the list decoder
+whose rules DESIGN.md §4.13 states: the GPU tests' second yardstick and the source of `pm`.
+
+Written from the standard and those rules; it shares no code with the kernels.  Bits are int8, LLRs
+log(P0/P1) in float64.  The two tables come from python_5gtoolbox_amd/data/nr_polar_tables.json.
+"""
+import json
+import math
+import os
+
+import numpy as np
+
+_DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "python_5gtoolbox_amd", "data",
+                     "nr_polar_tables.json")
+_T = {}
+# Table 5.4.1.1-1, sub-block interleaver pattern P(i)
+SUBBLOCK = [0, 1, 2, 4, 3, 5, 6, 7, 8, 16, 9, 17, 10, 18, 11, 19, 12, 20, 13, 21, 14, 22, 15, 23, 24, 25, 26, 28, 27,
+            29, 30, 31]
+CRC_POLY = {6: [1, 1, 0, 0, 0, 0, 1], 11: [1, 1, 1, 0, 0, 0, 1, 0, 0, 0, 0, 1],
+            24: [1, 1, 0, 1, 1, 0, 0, 1, 0, 1, 0, 1, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 1, 1, 1]}   # x^L .. x^0 (24: CRC24C)
+
+
+def tables():
+    if not _T:
+        with open(_DATA) as f:
+            t = json.load(f)
+        _T["Q"] = np.array(t["reliability_5_3_1_2_1"], np.int64)
+        _T["PI"] = np.array(t["interleaver_5_3_1_1_1"], np.int64)
+    return _T["Q"], _T["PI"]
+
+
+def crc_rem(bits, L):
+    """L-bit remainder of bits(x) * x^L by the generator, as a 0/1 list (MSB first)."""
+    g = CRC_POLY[L]
+    reg = [0] * L
+    for b in bits:
+        fb = reg[0] ^ int(b)
+        reg = reg[1:] + [0]
+        if fb:
+            reg = [r ^ c for r, c in zip(reg, g[1:])]
+    return reg
+
+
+def mask_bits(rnti, L):
+    return [(rnti >> (L - 1 - i)) & 1 for i in range(L)]
+
+
+def crc_attach(bits, L, rnti=0, pad=0):
+    """DL (pad = 1): 24 ones in front for the division, dropped again; CRC xor the rnti's low L bits."""
+    bits = [int(b) for b in bits]
+    r = crc_rem([1] * 24 * pad + bits, L)
+    return np.array(bits + [a ^ b for a, b in zip(r, mask_bits(rnti, L))], np.int8)
+
+
+def n_value(K, E, nMax):
+    c = (E - 1).bit_length()   # ceil(log2 E)
+    n1 = c - 1 if (8 * E <= 9 * (1 << (c - 1)) and 16 * K < 9 * E) else c
+    n2 = (8 * K - 1).bit_length()
+    return max(min(n1, n2, nMax), 5)
+
+
+def subblock(N):
+    return np.array([SUBBLOCK[(32 * i) // N] * (N // 32) + i % (N // 32) for i in range(N)])
+
+
+def mode(K, E, N):
+    return "rep" if E >= N else ("punct" if 16 * K <= 7 * E else "short")
+
+
+def construct(K, E, nMax):
+    """F (1 = frozen), qPC, N, nPC, nPCwm of §5.3.1.2 / §5.4.1.1."""
+    assert nMax in (9, 10)
+    N = 1 << n_value(K, E, nMax)
+    nPC = nPCwm = 0
+    if nMax == 10:
+        assert 18 <= K <= 25 or K > 30
+        if K <= 25:
+            nPC, nPCwm = 3, int(E - K + 3 > 192)
+    assert K + nPC <= E
+    Q, _ = tables()
+    QN = Q[Q < N]
+    J = subblock(N)
+    pre = set()
+    if E < N:
+        if mode(K, E, N) == "punct":
+            pre.update(J[:N - E].tolist())
+            pre.update(range((3 * N - 2 * E + 3) // 4 if 4 * E >= 3 * N else (9 * N - 4 * E + 15) // 16))
+        else:
+            pre.update(J[E:].tolist())
+    qI = [int(i) for i in QN[::-1] if int(i) not in pre][:K + nPC]
+    assert len(qI) == K + nPC
+    F = np.ones(N, np.int8)
+    F[qI] = 0
+    qPC = np.zeros(nPC, np.int16)
+    if nPC:
+        qPC[:nPC - nPCwm] = qI[len(qI) - (nPC - nPCwm):]
+        if nPCwm:
+            best = qI[:len(qI) - nPC]
+            w = [bin(i).count("1") for i in best]   # row weight of G_N is 2^popcount
+            qPC[nPC - 1] = best[w.index(min(w))]
+    return F, qPC, N, nPC, nPCwm
+
+
+def il_pattern(K):
+    """Pi(k) of §5.3.1.1: c'_k = c_Pi(k)."""
+    _, PI = tables()
+    assert K <= 164
+    return np.array([int(v) - (164 - K) for v in PI if v >= 164 - K])
+
+
+def layout(K, E, nMax, iIL, CRCLEN=24, padCRC=0, rnti=0):
+    """Everything position-like a coder needs (what ldpc5g_polar_plan builds)."""
+    F, qPC, N, nPC, nPCwm = construct(K, E, nMax)
+    info = [i for i in range(N) if F[i] == 0 and i not in qPC]
+    pil = il_pattern(K) if iIL else np.arange(K)
+    dep = np.argsort(pil)
+    ck_src = np.array(info)[dep]          # ck[i] sits at u[ck_src[i]]
+    d = dict(N=N, F=F, qPC=qPC, nPC=nPC, nPCwm=nPCwm, info=np.array(info), pil=pil, dep=dep, ck_src=ck_src,
+             mode=mode(K, E, N))
+    pc_sets = []
+    for p in qPC.tolist():
+        pc_sets.append([i for i in info if i < p and (p - i) % 5 == 0])
+    d["pc_sets"] = pc_sets
+    if iIL:   # bit c of CRC24C = parity of the ck whose unit vector's remainder has bit c, xor the mask
+        A = K - 24
+        rows = np.array([crc_rem([0] * n + [1] + [0] * (A - 1 - n), 24) for n in range(A)], np.int8).reshape(A, 24)
+        cm = np.zeros(24, np.int8)
+        if padCRC:
+            cm = np.array([a ^ b for a, b in zip(crc_rem([1] * 24 + [0] * A, 24), mask_bits(rnti, 24))], np.int8)
+        d["crc_rows"], d["crc_mask"] = rows, cm
+        d["crc_phase"] = {int(ck_src[A + c]): c for c in range(24)}
+    return d
+
+
+def encode(bits, E, nMax, iIL):
+    bits = np.asarray(bits).astype(np.int8)
+    K = bits.size
+    d = layout(K, E, nMax, iIL)
+    N = d["N"]
+    u = np.zeros(N, np.int8)
+    u[d["ck_src"]] = bits
+    for p, s in sorted(zip(d["qPC"].tolist(), d["pc_sets"])):
+        u[p] = np.bitwise_xor.reduce(u[s]) if s else 0
+    x = u.copy()
+    h = 1
+    while h < N:   # x = u G_N
+        x = x.reshape(-1, 2, h)
+        x[:, 0, :] ^= x[:, 1, :]
+        x = x.reshape(N)
+        h *= 2
+    return x
+
+
+def chan_il(E):
+    """Triangular channel interleaver of §5.4.1.3: f[k] = e[perm[k]]."""
+    T = 0
+    while T * (T + 1) // 2 < E:   # the smallest T with T(T+1)/2 >= E
+        T += 1
+    idx = -np.ones((T, T), np.int64)
+    k = 0
+    for r in range(T):
+        for c in range(T - r):
+            if k < E:
+                idx[r, c] = k
+            k += 1
+    return np.array([idx[r, c] for c in range(T) for r in range(T - c) if idx[r, c] >= 0])
+
+
+def rate_match(d, K, E, iBIL):
+    d = np.asarray(d)
+    N = d.size
+    y = d[subblock(N)]
+    m = mode(K, E, N)
+    e = y[np.arange(E) % N] if m == "rep" else (y[N - E:] if m == "punct" else y[:E])
+    return e[chan_il(E)] if iBIL else e
+
+
+def rate_recover(llr, K, N, iBIL, LLR_limit=20.0, reference_repetition=False):
+    llr = np.asarray(llr, np.float64)
+    E = llr.size
+    e = llr
+    if iBIL:
+        e = np.zeros(E)
+        e[chan_il(E)] = llr
+    y = np.zeros(N)
+    m = mode(K, E, N)
+    if m == "rep":
+        src = llr if reference_repetition else e   # the reference sums the LLRs it did not de-interleave
+        for o in range(0, E, N):
+            n = min(N, E - o)
+            y[:n] = y[:n] + src[o:o + n]
+    elif m == "punct":
+        y[N - E:] = e
+    else:
+        y[:E] = e
+        y[E:] = LLR_limit
+    out = np.zeros(N)
+    out[subblock(N)] = y
+    return out
+
+
+def bitrev(N):
+    n = N.bit_length() - 1
+    return np.array([int(format(i, "0%db" % n)[::-1], 2) for i in range(N)])
+
+
+class _State:
+    """L paths; layer lam (1..m) holds N >> lam branches: one LLR and the even/odd partial sums each."""
+
+    def __init__(self, N, L, llr0):
+        self.m = m = N.bit_length() - 1
+        self.P = [llr0] + [np.zeros((L, N >> lam)) for lam in range(1, m + 1)]
+        self.B = [None] + [np.zeros((L, N >> lam, 2), np.int8) for lam in range(1, m + 1)]
+        self.U = np.zeros((L, N), np.int8)
+        self.PM = np.zeros(L)
+        self.act = np.zeros(L, bool)
+        self.act[0] = True
+
+    def clone(self, s, t):
+        for lam in range(1, self.m + 1):
+            self.P[lam][t] = self.P[lam][s]
+            self.B[lam][t] = self.B[lam][s]
+        self.U[t] = self.U[s]
+        self.PM[t] = self.PM[s]
+
+    def llr_phase(self, p, ph):
+        m = self.m
+        low = 1 if ph == 0 else m - ((ph & -ph).bit_length() - 1)
+        for lam in range(low, m + 1):
+            src = self.P[0] if lam == 1 else self.P[lam - 1][p]
+            a, b = src[0::2], src[1::2]
+            if ((ph >> (m - lam)) & 1) == 0:
+                self.P[lam][p] = np.sign(a) * np.sign(b) * np.minimum(np.abs(a), np.abs(b))
+            else:
+                self.P[lam][p] = np.where(self.B[lam][p, :, 0] == 1, b - a, b + a)
+
+    def set_bit(self, p, ph, u):
+        self.U[p, ph] = u
+        self.B[self.m][p, 0, ph & 1] = u
+        v = self.P[self.m][p, 0]
+        if (v > 0 and u == 1) or (v < 0 and u == 0):
+            self.PM[p] = self.PM[p] + abs(v)
+
+    def bits_phase(self, p, ph):
+        lam = self.m
+        while ph & 1 and lam > 1:
+            e, o = self.B[lam][p, :, 0], self.B[lam][p, :, 1]
+            ph >>= 1
+            self.B[lam - 1][p, 0::2, ph & 1] = e ^ o
+            self.B[lam - 1][p, 1::2, ph & 1] = o
+            lam -= 1
+
+
+def decode(algo, llr, E, K, L, nMax, iIL, CRCLEN=24, padCRC=0, rnti=0):
+    """-> (ck int8[K] or [-1]*K, status, pm, info).  info counts what the fixtures must cover."""
+    algo = {"SC_optionB": "SC", "SCL_optionB": "SCL"}.get(algo, algo)
+    assert algo in ("SC", "SCL")
+    d = layout(K, E, nMax, iIL, CRCLEN, padCRC, rnti)
+    N, F = d["N"], d["F"]
+    llr = np.asarray(llr, np.float64)
+    assert llr.size == N
+    info = dict(early=False, crc_fail=False, not_best=False, pc_kills=0, median_ties=0, crc_kills=0)
+    fail = (-np.ones(K, np.int8), False, math.inf, info)
+    sc = algo == "SC"
+    if sc:
+        L = 1
+    S = _State(N, L, llr[bitrev(N)])
+    pcs = {int(p): s for p, s in zip(d["qPC"].tolist(), d["pc_sets"])}
+    for ph in range(N):
+        act = [p for p in range(L) if S.act[p]]
+        for p in act:
+            S.llr_phase(p, ph)
+        if F[ph]:
+            for p in act:
+                S.set_bit(p, ph, 0)
+        elif sc:
+            S.set_bit(0, ph, 0 if S.P[S.m][0, 0] > 0 else 1)
+        else:
+            v = S.P[S.m][:, 0]
+            n0 = S.PM + np.where(v > 0, 0.0, np.abs(v))
+            n1 = S.PM + np.where(v > 0, np.abs(v), 0.0)
+            A = len(act)
+            if 2 * A <= L:
+                for p in act:
+                    t = int(np.flatnonzero(~S.act)[0])
+                    S.clone(p, t)
+                    S.act[t] = True
+                    S.set_bit(p, ph, 0)
+                    S.set_bit(t, ph, 1)
+            else:
+                s = sorted([n0[p] for p in act] + [n1[p] for p in act])
+                thr = (s[A - 1] + s[A]) / 2
+                if any(n0[p] == thr or n1[p] == thr for p in act):
+                    info["median_ties"] += 1
+                for p in act:
+                    if n0[p] >= thr and n1[p] >= thr:
+                        S.act[p] = False
+                act = [p for p in act if S.act[p]]
+                for p in act:
+                    if (n0[p] < thr) != (n1[p] < thr):
+                        S.set_bit(p, ph, 0 if n0[p] < thr else 1)
+                for p in act:
+                    if n0[p] < thr and n1[p] < thr:
+                        t = int(np.flatnonzero(~S.act)[0])
+                        S.clone(p, t)
+                        S.act[t] = True
+                        S.set_bit(p, ph, 0)
+                        S.set_bit(t, ph, 1)
+            act = [p for p in range(L) if S.act[p]]
+            if ph in pcs:
+                for p in act:
+                    want = int(np.bitwise_xor.reduce(S.U[p, pcs[ph]])) if pcs[ph] else 0
+                    if S.U[p, ph] != want:
+                        S.act[p] = False
+                        info["pc_kills"] += 1
+            elif iIL and ph in d["crc_phase"]:
+                c = d["crc_phase"][ph]
+                for p in act:
+                    ck = S.U[p, d["ck_src"]]
+                    want = (int(ck[:K - 24] @ d["crc_rows"][:, c]) + int(d["crc_mask"][c])) & 1
+                    if ck[K - 24 + c] != want:
+                        S.act[p] = False
+                        info["crc_kills"] += 1
+            if not S.act.any():
+                info["early"] = True
+                return fail
+        if ph & 1:
+            for p in range(L):
+                if S.act[p]:
+                    S.bits_phase(p, ph)
+    order = sorted((p for p in range(L) if S.act[p]), key=lambda p: (S.PM[p], p))
+    if sc or iIL:
+        p = order[0]
+        return S.U[p, d["ck_src"]].copy(), True, float(S.PM[p]), info
+    for j, p in enumerate(order):
+        ck = S.U[p, d["ck_src"]]
+        want = [a ^ b for a, b in zip(crc_rem(ck[:K - CRCLEN], CRCLEN), mask_bits(rnti, CRCLEN))]
+        if ck[K - CRCLEN:].tolist() == want:
+            info["not_best"] = j > 0
+            return ck.copy(), True, float(S.PM[p]), info
+    info["crc_fail"] = True
+    return fail
+
+
+def cbsegment(bits, Euci):
+    """§5.2.1 / §6.3.1.2.1: -> (C x (A' + L) blocks with CRC, C, E per block)."""
+    bits = np.asarray(bits).astype(np.int8)
+    A = bits.size
+    assert 12 <= A <= 1706
+    if A >= 1013 or (A >= 360 and Euci >= 1088):
+        assert Euci % 2 == 0
+        C, L = 2, 11
+        if A % 2:
+            bits = np.concatenate(([0], bits)).astype(np.int8)
+        parts = bits.reshape(2, -1)
+    else:
+        C, L, parts = 1, (6 if A <= 19 else 11), bits.reshape(1, -1)
+    return np.stack([crc_attach(p, L) for p in parts]), C, Euci // C
