@@ -111,6 +111,13 @@ void clear_error();
 const char* err_text();   // message of the last fail() on this thread
 int zc_index(int Zc);
 int check_hip(hipError_t e, const char* what);
+inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
+inline bool smooth235(int n) {   // n = 2^a 3^b 5^c: the rb_size of a transform-precoded PUSCH (38.211 6.3.1.4)
+    if (n < 1) return false;
+    for (int f = 2; f <= 5; f += 1 + (f > 2))
+        while (n % f == 0) n /= f;
+    return n == 1;
+}
 
 // Raise kernel KERN's dynamic-LDS limit to `lds` bytes once per device: hipFuncSetAttribute is a
 // host-side round trip that the per-codeblock drop-in calls would otherwise pay on every launch.

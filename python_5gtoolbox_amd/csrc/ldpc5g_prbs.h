@@ -1,8 +1,9 @@
 // ldpc5g_prbs.h — the parts of the Gold sequence c(n) of py5gphy/common/nrPRBS.py:5-25 (gen_nrPRBS)
 // that ldpc5g_phy.hip (scrambling codes) and ldpc5g_slot.hip (DMRS sequences) share: the constexpr
 // generator of the jump-ahead matrices T^(2^i), the 32-position step, and the row-form device
-// table with the wave-wide jump that ldpc5g_slot.hip and ldpc5g_tp.hip (hopping) use.  ldpc5g_phy.hip
-// builds its column-form device table from the generator itself.
+// table with the wave-wide jump that ldpc5g_slot.hip uses for both of its sequence sources (the
+// Gold DMRS bits; the group / sequence hopping of the low-PAPR DMRS).  ldpc5g_phy.hip builds its
+// column-form device table from the generator itself.
 #pragma once
 #include <stdint.h>
 

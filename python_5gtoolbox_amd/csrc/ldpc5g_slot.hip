@@ -2,22 +2,30 @@
 // channel estimator's H_LS and the equaliser's interleaved y on the other, batched over slots:
 //   DMRS least-squares estimate ........ py5gphy/nr_pdsch/nr_pdsch_dmrs.py:139-227 (pdsch_dmrs_LS_est),
 //                                        py5gphy/nr_pusch/nr_pusch_dmrs.py:107-200 (pusch_dmrs_LS_est)
-//   DMRS sequence r(n) ................. nr_pdsch_dmrs.py:244-256 (_gen_seq), nrPRBS.py:5-25
+//   DMRS sequence r(n), Gold / QPSK .... nr_pdsch_dmrs.py:244-256 (_gen_seq), nrPRBS.py:5-25
+//   DMRS sequence r(n), low-PAPR ....... nr_pusch_dmrs.py:216-249 (_gen_seq_with_transform_precoding)
 //   extraction of the allocation ....... py5gphy/nr_pdsch/nrpdsch_resource_mapping.py:87-129
-//   DMRS generation and mapping ........ nr_pdsch_dmrs.py:90-120 (pdsch_dmrs_process)
+//   DMRS generation and mapping ........ nr_pdsch_dmrs.py:90-120 (pdsch_dmrs_process),
+//                                        nr_pusch_dmrs.py:66-101 (transform precoding)
 //   data precoding and RE mapping ...... py5gphy/nr_pdsch/nr_pdsch_process.py:27-42,
 //                                        nrpdsch_resource_mapping.py:58-85
+// (ldpc5g_slot_rx_frontend / ldpc5g_slot_map and their _tp forms, include/ldpc5g.h).
 // All three kernels are HBM-bound copies with a little arithmetic: one lane per resource element
 // (extraction, data mapping) or per DMRS resource element (LS, DMRS mapping).  Loads run along the
 // subcarrier axis of one antenna plane, so a wave reads contiguous runs; a lane stores its Nr (or
 // Nr*Nt) contiguous output elements with 16-byte stores where size and alignment allow.
-// The DMRS sequence is made on the device: cinit from slots[t], then every wave jumps both
-// m-sequences to its own first bit with the jump-ahead matrices of ldpc5g_prbs.h (applied across
-// the lanes, one ballot per matrix) and steps out the 256 bits (4 per DMRS RE) its lanes need.
+// The LS and map kernels take the DMRS sequence as a compile-time source type (GoldSeq,
+// LowPaprSeq): a wave-uniform part that every lane of a wave runs before any lane leaves, and a
+// per-lane part that yields r(2k), r(2k+1).  Both are made on the device from slots[t].  Gold: cinit,
+// then every wave jumps both m-sequences to its own first bit with the jump-ahead matrices of
+// ldpc5g_prbs.h (applied across the lanes, one ballot per matrix) and steps out the 256 bits (4 per
+// DMRS RE) its lanes need.  Low-PAPR: the hopping (u, v) from the same jump, then one point of
+// ldpc5g_lowpapr.h per sequence element, or the caller's base sequence.
 #include <math.h>
 #include <stdint.h>
 
 #include "ldpc5g_common.h"
+#include "ldpc5g_lowpapr.h"
 #include "ldpc5g_prbs.h"
 
 namespace ldpc5g_impl {
@@ -26,41 +34,109 @@ namespace {
 constexpr int kSlotThreads = 256;
 constexpr int kSlotSyms = 14;
 
-struct SlotDmrs {          // by value: everything about the DMRS that is the same for every slot
+struct SlotDmrs {          // by value: what is the same for every slot and either sequence
     int32_t carrier_re, rb_start, rb_size, S;
     int32_t sym[4];        // DMRS symbol indices
     int32_t port[4];       // port - 1000 of layer / transmit index p
-    int32_t nid, nscid;
     double inv;            // LS: 1 / (2 scaling)
-    float scaling;         // map: float32(scaling)
+    double scaling;        // map
 };
 
 __device__ __forceinline__ int dmrs_sym(const SlotDmrs& c, int m) {   // c.sym[m] without a dynamic index
     return m == 0 ? c.sym[0] : m == 1 ? c.sym[1] : m == 2 ? c.sym[2] : c.sym[3];
 }
 
-// cinit of nr_pdsch_dmrs.py:249-251 for slot number `slot` and symbol `sym`
-__device__ __forceinline__ uint32_t dmrs_cinit(const SlotDmrs& c, int32_t slot, int sym) {
-    const uint64_t a = (uint64_t)(uint32_t)(14 * slot + sym + 1) * (uint64_t)(2 * c.nid + 1);
-    return (uint32_t)(((a << 17) + (uint64_t)(2 * c.nid + c.nscid)) & 0x7FFFFFFFull);
-}
+// ------------------------------------------------------------------ the two sequence sources
+// A source S has
+//   S::Wave wave(c, slot, sym, k0)   the wave-uniform part for DMRS symbol `sym` of slot number
+//                                    `slot`, k0 the workgroup's first DMRS RE.  It ends in
+//                                    prbs_jump_wave: every lane of the wave must be active.
+//   pair(c, w, t, m, k, r)           the lane's r(2k) = r[0] + j r[1], r(2k+1) = r[2] + j r[3] of DMRS
+//                                    symbol m of slot t, in float64 (LS) or S::MapReal (map)
+//   S::MapReal                       the type in which the map forms scaling * r before float32
+//   S::kAcc0                         what the precoding sum over the layers starts from
+//   S::kOneLayer                     only Nt = NL = 1 is instantiated
+//   map_port(c, l)                   port - 1000 of layer l of the map
 
-// The lane's four sequence bits c(bit0 + 4 lane .. + 3), lane = threadIdx.x % 64, of the sequence
-// started by cinit; bit0 is wave-uniform.  Each wave makes its own 256 bits: the jump above, then
-// eight uniform 32-bit steps.  No LDS, no barrier.
-__device__ __forceinline__ uint32_t dmrs_lane_bits(uint32_t cinit, uint32_t bit0) {
-    const uint32_t n = __builtin_amdgcn_readfirstlane(1600u + bit0);
-    uint32_t s1 = prbs_jump_wave(0, 1u, n);
-    uint32_t s2 = prbs_jump_wave(1, __builtin_amdgcn_readfirstlane(cinit), n);
-    const uint32_t g = (threadIdx.x >> 3) & 7u;
-    uint32_t w = 0;
+// Gold sequence, QPSK (nr_pdsch_dmrs.py:244-256).  w: the lane's four bits c(2(2k)) .. c(2(2k+1)+1).
+struct GoldSeq {
+    int32_t nid, nscid;
+    using Wave = uint32_t;
+    using MapReal = float;                    // nrModulate's complex64 and float32 products
+    static constexpr float kAcc0 = 0.0f;      // the reference's matrix product: a sum from zero
+    static constexpr bool kOneLayer = false;
+    static __device__ __forceinline__ int map_port(const SlotDmrs&, int l) { return l; }   // the reference's row l
+
+    // cinit of nr_pdsch_dmrs.py:249-251, then the bits c(bit0 + 4 lane .. + 3), lane = threadIdx.x %
+    // 64, bit0 the wave's first.  Each wave makes its own 256 bits: the jump, then eight uniform
+    // 32-bit steps.  No LDS, no barrier.
+    __device__ __forceinline__ Wave wave(const SlotDmrs& c, int32_t slot, int sym, int k0) const {
+        const uint64_t a = (uint64_t)(uint32_t)(14 * slot + sym + 1) * (uint64_t)(2 * nid + 1);
+        const uint32_t cinit = (uint32_t)(((a << 17) + (uint64_t)(2 * nid + nscid)) & 0x7FFFFFFFull);
+        const uint32_t bit0 = (uint32_t)(12 * c.rb_start + 4 * (k0 + (int)(threadIdx.x & ~63u)));
+        const uint32_t n = __builtin_amdgcn_readfirstlane(1600u + bit0);
+        uint32_t s1 = prbs_jump_wave(0, 1u, n);
+        uint32_t s2 = prbs_jump_wave(1, __builtin_amdgcn_readfirstlane(cinit), n);
+        const uint32_t g = (threadIdx.x >> 3) & 7u;
+        uint32_t w = 0;
 #pragma unroll
-    for (uint32_t i = 0; i < 8; ++i) {
-        const uint32_t c = prbs_step32(s1, false) ^ prbs_step32(s2, true);
-        w = g == i ? c : w;
+        for (uint32_t i = 0; i < 8; ++i) {
+            const uint32_t b = prbs_step32(s1, false) ^ prbs_step32(s2, true);
+            w = g == i ? b : w;
+        }
+        return (w >> (4 * (threadIdx.x & 7))) & 15u;
     }
-    return (w >> (4 * (threadIdx.x & 7))) & 15u;
-}
+    template <typename F>
+    __device__ __forceinline__ void pair(const SlotDmrs&, Wave b, int, int, int, F (&r)[4]) const {
+        F q;
+        if constexpr (sizeof(F) == 8) q = 0.70710678118654752440;   // 1 / sqrt(2)
+        else q = 1.0f / (float)sqrt(2.0);                           // nrModulate's complex64 division by sqrt(2)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = ((b >> i) & 1u) ? -q : q;
+    }
+};
+
+// Low-PAPR sequence rbar_{u,v}, alpha = 0 (nr_pusch_dmrs.py:216-249), or the caller's base_seq.
+struct LowPaprSeq {
+    int32_t id, hopping;       // nPuschID; 0 neither, 1 group, 2 sequence hopping
+    int32_t MZC, NZC;          // 6 rb_size and the largest prime below it
+    const double2* base_seq;   // [T][S][MZC] instead of the generated sequence, or null
+    struct Wave {
+        int u, v;
+    };
+    using MapReal = double;                   // float32(double scaling * double r)
+    static constexpr float kAcc0 = -0.0f;     // one layer, one product, no sum: x + -0 is x, sign kept
+    static constexpr bool kOneLayer = true;
+    static __device__ __forceinline__ int map_port(const SlotDmrs& c, int) { return c.port[0]; }
+
+    // (u, v) of the symbol.  The Gold bits c(n) are the low bits of the two jumped states: bit i of a
+    // state at n is x(n + i).  The reference makes one frame of bits (slot < 20); a position past the
+    // jump tables' 8192 wraps instead of reading beyond.  A uniform branch around the jumps.
+    __device__ __forceinline__ Wave wave(const SlotDmrs&, int32_t slot, int sym, int) const {
+        Wave w{id % 30, 0};
+        if (base_seq) return w;
+        const uint32_t pos = (uint32_t)(14 * slot + sym);
+        if (hopping == 1) {
+            const uint32_t n = __builtin_amdgcn_readfirstlane((1600u + 8u * pos) & 8191u);
+            const uint32_t s1 = prbs_jump_wave(0, 1u, n), s2 = prbs_jump_wave(1, (uint32_t)(id / 30), n);
+            w.u = (int)((((s1 ^ s2) & 255u) % 30u + (uint32_t)id) % 30u);
+        } else if (hopping == 2 && MZC >= 72) {
+            const uint32_t n = __builtin_amdgcn_readfirstlane((1600u + pos) & 8191u);
+            const uint32_t s1 = prbs_jump_wave(0, 1u, n), s2 = prbs_jump_wave(1, (uint32_t)id, n);
+            w.v = (int)((s1 ^ s2) & 1u);
+        }
+        return w;
+    }
+    __device__ __forceinline__ void pair(const SlotDmrs& c, Wave w, int t, int m, int k, double (&r)[4]) const {
+        if (base_seq) {
+            const double2* b = base_seq + ((int64_t)t * c.S + m) * MZC + 2 * k;
+            r[0] = b[0].x, r[1] = b[0].y, r[2] = b[1].x, r[3] = b[1].y;
+        } else {
+            low_papr_point(w.u, w.v, 2 * k, MZC, NZC, r[0], r[1]);
+            low_papr_point(w.u, w.v, 2 * k + 1, MZC, NZC, r[2], r[3]);
+        }
+    }
+};
 
 // CNT consecutive complex elements to / from p; v16: p is 16-byte aligned (complex128 always is)
 template <typename C, int CNT>
@@ -96,10 +172,11 @@ __device__ __forceinline__ void load_run(const C* p, C (&v)[CNT], bool v16) {
 // One lane per DMRS RE k of DMRS symbol m of slot t.  Per antenna the lane loads the four REs
 // 4k .. 4k+3 once (32 or 64 contiguous bytes; a wave reads one contiguous run of the plane): they
 // serve both CDM groups.  h_ls[t][m][k][r][p] = (Y[4k+d] conj(r(2k)) +- Y[4k+d+2] conj(r(2k+1)))
-// * inv, d = (port/2) % 2, minus for odd ports (nr_pdsch_dmrs.py:207-215), in float64.
-template <typename C, int NR, int NT>
+// * inv, d = (port/2) % 2, minus for odd ports (nr_pdsch_dmrs.py:207-215, nr_pusch_dmrs.py:174-190),
+// in float64.
+template <typename C, int NR, int NT, typename Seq>
 __global__ __launch_bounds__(kSlotThreads) void slot_ls_kernel(const C* __restrict__ grid, int64_t ldg,
-                                                               const int32_t* __restrict__ slots, SlotDmrs c,
+                                                               const int32_t* __restrict__ slots, SlotDmrs c, Seq q,
                                                                C* __restrict__ h_ls, int64_t ldh, int ld16,
                                                                int st16) {
     using R = decltype(C{}.x);
@@ -114,27 +191,26 @@ __global__ __launch_bounds__(kSlotThreads) void slot_ls_kernel(const C* __restri
 #pragma unroll
         for (int r = 0; r < NR; ++r) load_run<C, 4>(src + (int64_t)r * kSlotSyms * c.carrier_re, Y[r], ld16 != 0);
     }
-    const uint32_t b = dmrs_lane_bits(dmrs_cinit(c, slots[t], sym),
-                                      (uint32_t)(12 * c.rb_start + 4 * (k0 + (int)(threadIdx.x & ~63u))));
+    const typename Seq::Wave w = q.wave(c, slots[t], sym, k0);   // before any lane leaves
     if (k >= N) return;
-    const double q = 0.70710678118654752440;   // 1 / sqrt(2)
-    // conj(r(2k)) = a0 - j b0, conj(r(2k+1)) = a1 - j b1
-    const double a0 = (b & 1u) ? -q : q, b0 = (b & 2u) ? -q : q;
-    const double a1 = (b & 4u) ? -q : q, b1 = (b & 8u) ? -q : q;
+    double s[4];   // conj(r(2k)) = s[0] - j s[1], conj(r(2k+1)) = s[2] - j s[3]
+    q.pair(c, w, t, m, k, s);
     C out[NR * NT];
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
-        double d0r[2], d0i[2], d1r[2], d1i[2];   // [delta]
+        double d0r[2], d0i[2], d1r[2], d1i[2];   // [delta]; a single layer fills only [0], with its own delta
 #pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            const double y0r = (double)Y[r][d].x, y0i = (double)Y[r][d].y;
-            const double y1r = (double)Y[r][d + 2].x, y1i = (double)Y[r][d + 2].y;
-            d0r[d] = y0r * a0 + y0i * b0, d0i[d] = y0i * a0 - y0r * b0;
-            d1r[d] = y1r * a1 + y1i * b1, d1i[d] = y1i * a1 - y1r * b1;
+        for (int d = 0; d < (NT == 1 ? 1 : 2); ++d) {
+            const bool up = NT == 1 ? (c.port[0] >> 1) & 1 : d;
+            const C lo0 = Y[r][0], lo1 = Y[r][2], up0 = Y[r][1], up1 = Y[r][3];   // read all, then choose values
+            const double y0r = (double)(up ? up0.x : lo0.x), y0i = (double)(up ? up0.y : lo0.y);
+            const double y1r = (double)(up ? up1.x : lo1.x), y1i = (double)(up ? up1.y : lo1.y);
+            d0r[d] = y0r * s[0] + y0i * s[1], d0i[d] = y0i * s[0] - y0r * s[1];
+            d1r[d] = y1r * s[2] + y1i * s[3], d1i[d] = y1i * s[2] - y1r * s[3];
         }
 #pragma unroll
         for (int p = 0; p < NT; ++p) {
-            const int d = (c.port[p] >> 1) & 1;
+            const int d = NT == 1 ? 0 : (c.port[p] >> 1) & 1;
             const bool odd = c.port[p] & 1;
             const double e0r = d ? d0r[1] : d0r[0], e0i = d ? d0i[1] : d0i[0];
             const double e1r = d ? d1r[1] : d1r[0], e1i = d ? d1i[1] : d1i[0];
@@ -171,14 +247,15 @@ struct SlotPrecode {
 // blockIdx.y == 0: one lane per data RE i.  x = sym[t][i*NL .. i*NL + NL-1] (the layer mapping of
 // nr_pdsch_process.py:27-32), grid[t][a][re_idx[i]'s position] = sum_l w[a][l] x[l] in float32,
 // l ascending (identity: x[a], or 0 for a >= NL).  An index outside 0 .. 14*12*rb - 1 writes nothing.
-// blockIdx.y == 1 + m: one lane per DMRS RE k of DMRS symbol m.  Layer l is port 1000 + l: at RE
-// 4k + d and 4k + d + 2, d = (l/2) % 2, it sends float32(scaling) * r(2k) and
-// float32(scaling * (1 - 2 (l % 2))) * r(2k+1) (nr_pdsch_dmrs.py:96-106), precoded the same way.
+// blockIdx.y == 1 + m: one lane per DMRS RE k of DMRS symbol m.  Layer l on port map_port(l): at RE
+// 4k + d and 4k + d + 2, d = (port/2) % 2, it sends float32(scaling r(2k)) and float32(+- scaling
+// r(2k+1)), minus for odd ports, the products in Seq::MapReal (nr_pdsch_dmrs.py:96-106,
+// nr_pusch_dmrs.py:76-101), precoded the same way; a layer of the other CDM group adds signed zeros.
 // Only the REs of CDM groups that carry a layer are written.
-template <int NA, int NL>
+template <int NA, int NL, typename Seq>
 __global__ __launch_bounds__(kSlotThreads) void slot_map_kernel(const float2* __restrict__ sym, int64_t ldsym,
                                                                 const int32_t* __restrict__ re_idx, int64_t nre,
-                                                                const int32_t* __restrict__ slots, SlotDmrs c,
+                                                                const int32_t* __restrict__ slots, SlotDmrs c, Seq q,
                                                                 SlotPrecode P, float2* __restrict__ grid,
                                                                 int64_t ldg, int ld16) {
     const int t = blockIdx.z;
@@ -186,7 +263,7 @@ __global__ __launch_bounds__(kSlotThreads) void slot_map_kernel(const float2* __
     const int nre_sym = 12 * c.rb_size;
     auto precode = [&](const float2 (&x)[NL], int a) {
         if (P.identity) return a < NL ? x[a < NL ? a : 0] : make_float2(0.0f, 0.0f);
-        float re = 0.0f, im = 0.0f;
+        float re = Seq::kAcc0, im = Seq::kAcc0;
 #pragma unroll
         for (int l = 0; l < NL; ++l) {
             re += P.w[a][l].x * x[l].x - P.w[a][l].y * x[l].y;
@@ -213,25 +290,28 @@ __global__ __launch_bounds__(kSlotThreads) void slot_map_kernel(const float2* __
     if (k0 >= N) return;   // uniform: the launch is as wide as the data part
     const int k = k0 + (int)threadIdx.x;
     const int sm = dmrs_sym(c, m);
-    const uint32_t b = dmrs_lane_bits(dmrs_cinit(c, slots[t], sm),
-                                      (uint32_t)(12 * c.rb_start + 4 * (k0 + (int)(threadIdx.x & ~63u))));
+    const typename Seq::Wave w = q.wave(c, slots[t], sm, k0);   // before any lane leaves
     if (k >= N) return;
-    const float q = 1.0f / (float)sqrt(2.0);   // nrModulate's complex64 division by sqrt(2)
-    const float2 r0 = make_float2((b & 1u) ? -q : q, (b & 2u) ? -q : q);
-    const float2 r1 = make_float2((b & 4u) ? -q : q, (b & 8u) ? -q : q);
+    using F = typename Seq::MapReal;
+    F r[4];
+    q.pair(c, w, t, m, k, r);
+    const F sc = (F)c.scaling;
     float2* dst = g + (int64_t)sm * c.carrier_re + 12 * c.rb_start + 4 * k;
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
-        if (d == 1 && NL <= 2) break;   // layers 2, 3 are the second CDM group
+        bool used = false;
         float2 x0[NL], x1[NL];
 #pragma unroll
         for (int l = 0; l < NL; ++l) {
-            const bool mine = ((l >> 1) & 1) == d;
-            const float s0 = mine ? c.scaling : 0.0f;
-            const float s1 = mine ? ((l & 1) ? -c.scaling : c.scaling) : 0.0f;
-            x0[l] = make_float2(s0 * r0.x, s0 * r0.y);
-            x1[l] = make_float2(s1 * r1.x, s1 * r1.y);
+            const int port = Seq::map_port(c, l);
+            const bool mine = ((port >> 1) & 1) == d;
+            used |= mine;
+            const F s0 = mine ? sc : (F)0;
+            const F s1 = mine ? ((port & 1) ? -sc : sc) : (F)0;
+            x0[l] = make_float2((float)(s0 * r[0]), (float)(s0 * r[1]));
+            x1[l] = make_float2((float)(s1 * r[2]), (float)(s1 * r[3]));
         }
+        if (!used) continue;
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
             dst[(int64_t)a * kSlotSyms * c.carrier_re + d] = precode(x0, a);
@@ -241,8 +321,9 @@ __global__ __launch_bounds__(kSlotThreads) void slot_map_kernel(const float2* __
 }
 
 // ------------------------------------------------------------------------------ host checks
+// what every entry point checks of the allocation and the DMRS symbols
 int check_dmrs(SlotDmrs& c, int32_t T, int32_t carrier_re, int32_t rb_start, int32_t rb_size, int32_t S,
-               const int32_t* sym_idx, int32_t nNIDnSCID, int32_t nSCID, int32_t num_cdm_groups) {
+               const int32_t* sym_idx) {
     if (T < 1 || T > 65535) return fail(LDPC5G_ESIZE, "T=%d outside 1..65535", T);
     if (carrier_re < 12 || carrier_re % 12 || carrier_re / 12 > 275)
         return fail(LDPC5G_ESIZE, "carrier_re=%d: a multiple of 12 up to 275 PRB", carrier_re);
@@ -254,24 +335,46 @@ int check_dmrs(SlotDmrs& c, int32_t T, int32_t carrier_re, int32_t rb_start, int
     for (int m = 0; m < S; ++m)
         if (sym_idx[m] < 0 || sym_idx[m] > 13 || (m > 0 && sym_idx[m] <= sym_idx[m - 1]))
             return fail(LDPC5G_ESIZE, "sym_idx[%d]=%d: strictly ascending in 0..13", m, sym_idx[m]);
+    c.carrier_re = carrier_re, c.rb_start = rb_start, c.rb_size = rb_size, c.S = S;
+    for (int m = 0; m < 4; ++m) c.sym[m] = m < S ? sym_idx[m] : 0;
+    return LDPC5G_OK;
+}
+
+void set_scaling(SlotDmrs& c, int num_cdm_groups) {   // nr_pdsch_dmrs.py:171-174, nr_pusch_dmrs.py:150-154
+    c.scaling = num_cdm_groups == 1 ? 1.0 : pow(10.0, -3.0 / 20.0);
+    c.inv = 1.0 / (2.0 * c.scaling);
+}
+
+int check_gold(SlotDmrs& c, GoldSeq& q, int32_t nNIDnSCID, int32_t nSCID, int32_t num_cdm_groups) {
     if (nNIDnSCID < 0 || nNIDnSCID > 65535) return fail(LDPC5G_ESIZE, "nNIDnSCID=%d outside 0..65535", nNIDnSCID);
     if (nSCID < 0 || nSCID > 1) return fail(LDPC5G_ESIZE, "nSCID=%d outside 0..1", nSCID);
     if (num_cdm_groups < 1 || num_cdm_groups > 2)
         return fail(LDPC5G_ESIZE, "num_cdm_groups=%d outside 1..2 (DMRS configuration type 1)", num_cdm_groups);
-    c.carrier_re = carrier_re, c.rb_start = rb_start, c.rb_size = rb_size, c.S = S;
-    for (int m = 0; m < 4; ++m) c.sym[m] = m < S ? sym_idx[m] : 0;
-    c.nid = nNIDnSCID, c.nscid = nSCID;
-    const double scaling = num_cdm_groups == 1 ? 1.0 : pow(10.0, -3.0 / 20.0);   // nr_pdsch_dmrs.py:171-174
-    c.inv = 1.0 / (2.0 * scaling);
-    c.scaling = (float)scaling;
+    q.nid = nNIDnSCID, q.nscid = nSCID;
+    set_scaling(c, num_cdm_groups);
     return LDPC5G_OK;
 }
 
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
+// after check_dmrs: one layer on `port`, NumCDMGroupsWithoutData == 2
+int check_low_papr(SlotDmrs& c, LowPaprSeq& q, int32_t port, int32_t nPuschID, int32_t hopping, const void* base_seq) {
+    if (!smooth235(c.rb_size)) return fail(LDPC5G_ESIZE, "rb_size=%d: 2^a 3^b 5^c in 1..275 (38.211 6.3.1.4)", c.rb_size);
+    if (port < 0 || port > 3) return fail(LDPC5G_ESIZE, "port=%d: port 1000..1003 as 0..3", port);
+    if (nPuschID < 0 || nPuschID > 1007) return fail(LDPC5G_ESIZE, "nPuschID=%d outside 0..1007", nPuschID);
+    if (hopping < 0 || hopping > 2) return fail(LDPC5G_ESIZE, "hopping=%d outside 0..2 (neither, group, sequence)", hopping);
+    if (c.rb_size <= 4 && !base_seq)
+        return fail(LDPC5G_ESIZE, "base_seq is null at rb_size=%d: the sequences of length 6..24 are tables "
+                                  "(38.211 5.2.2.2), pass them", c.rb_size);
+    if (!aligned(base_seq, 16)) return fail(LDPC5G_ESIZE, "base_seq is not aligned to its element size");
+    c.port[0] = port;
+    q.id = nPuschID, q.hopping = hopping, q.MZC = 6 * c.rb_size, q.NZC = low_papr_nzc(q.MZC);
+    q.base_seq = (const double2*)base_seq;
+    set_scaling(c, 2);
+    return LDPC5G_OK;
+}
 
-template <typename C>
-int launch_frontend(const void* grid, int64_t ldg, const int32_t* slots, int T, const SlotDmrs& c, int Nr, int Nt,
-                    void* h_ls, int64_t ldh, void* y, int64_t ldy, hipStream_t st) {
+template <typename C, typename Seq>
+int launch_frontend(const void* grid, int64_t ldg, const int32_t* slots, int T, const SlotDmrs& c, const Seq& q, int Nr,
+                    int Nt, void* h_ls, int64_t ldh, void* y, int64_t ldy, hipStream_t st) {
     const bool c64 = sizeof(C) == 8;
     const int ld16 = !c64 || (aligned(grid, 16) && ldg % 2 == 0);
     if (h_ls) {
@@ -279,13 +382,14 @@ int launch_frontend(const void* grid, int64_t ldg, const int32_t* slots, int T, 
         const int st16 = !c64 || (aligned(h_ls, 16) && ldh % 2 == 0);
         const dim3 g((unsigned)((N + kSlotThreads - 1) / kSlotThreads), c.S, T), b(kSlotThreads);
 #define LDPC5G_LS(NR, NT) \
-    hipLaunchKernelGGL((slot_ls_kernel<C, NR, NT>), g, b, 0, st, (const C*)grid, ldg, slots, c, (C*)h_ls, ldh, ld16, st16)
-#define LDPC5G_LS_NT(NR)                        \
-    switch (Nt) {                               \
-        case 1: LDPC5G_LS(NR, 1); break;        \
-        case 2: LDPC5G_LS(NR, 2); break;        \
-        case 3: LDPC5G_LS(NR, 3); break;        \
-        default: LDPC5G_LS(NR, 4); break;       \
+    hipLaunchKernelGGL((slot_ls_kernel<C, NR, NT, Seq>), g, b, 0, st, (const C*)grid, ldg, slots, c, q, (C*)h_ls, ldh, ld16, st16)
+#define LDPC5G_LS_NT(NR)                            \
+    if constexpr (Seq::kOneLayer) LDPC5G_LS(NR, 1); \
+    else switch (Nt) {                              \
+        case 1: LDPC5G_LS(NR, 1); break;            \
+        case 2: LDPC5G_LS(NR, 2); break;            \
+        case 3: LDPC5G_LS(NR, 3); break;            \
+        default: LDPC5G_LS(NR, 4); break;           \
     }
         if (Nr == 1) { LDPC5G_LS_NT(1) } else if (Nr == 2) { LDPC5G_LS_NT(2) } else { LDPC5G_LS_NT(4) }
 #undef LDPC5G_LS_NT
@@ -306,20 +410,67 @@ int launch_frontend(const void* grid, int64_t ldg, const int32_t* slots, int T, 
     return LDPC5G_OK;
 }
 
-template <int NA>
-void launch_map_na(int NL, dim3 g, hipStream_t st, const float2* sym, int64_t ldsym, const int32_t* re_idx,
-                   int64_t nre, const int32_t* slots, const SlotDmrs& c, const SlotPrecode& P, float2* grid,
-                   int64_t ldg, int ld16) {
-    const dim3 b(kSlotThreads);
-#define LDPC5G_MAP(NL_) \
-    hipLaunchKernelGGL((slot_map_kernel<NA, NL_>), g, b, 0, st, sym, ldsym, re_idx, nre, slots, c, P, grid, ldg, ld16)
-    switch (NL) {
-        case 1: LDPC5G_MAP(1); break;
-        case 2: LDPC5G_MAP(2); break;
-        case 3: LDPC5G_MAP(3); break;
-        default: LDPC5G_MAP(4); break;
+// the dtype, antenna, stride, null and alignment checks of a front-end call, then its launches
+template <typename Seq>
+int run_frontend(const SlotDmrs& c, const Seq& q, const void* grid, int64_t ldgrid, int32_t in_dtype,
+                 const int32_t* slots, int32_t T, int32_t Nr, int32_t Nt, void* h_ls, int64_t ldh, void* y, int64_t ldy,
+                 void* stream) {
+    if (in_dtype != LDPC5G_F32 && in_dtype != LDPC5G_F64) return fail(LDPC5G_ESIZE, "bad grid dtype %d", in_dtype);
+    if (Nr != 1 && Nr != 2 && Nr != 4) return fail(LDPC5G_ESIZE, "Nr=%d: supported Nr in {1, 2, 4}", Nr);
+    const int64_t N = 3 * (int64_t)c.rb_size;
+    if (ldgrid < (int64_t)Nr * kSlotSyms * c.carrier_re)
+        return fail(LDPC5G_ESIZE, "grid stride %lld shorter than Nr*14*carrier_re", (long long)ldgrid);
+    if (h_ls && ldh < c.S * N * Nr * Nt) return fail(LDPC5G_ESIZE, "h_ls stride %lld shorter than S*N*Nr*Nt", (long long)ldh);
+    if (y && ldy < kSlotSyms * 4 * N * Nr) return fail(LDPC5G_ESIZE, "y stride %lld shorter than 14*12*rb_size*Nr", (long long)ldy);
+    if (!grid || !slots) return fail(LDPC5G_ESIZE, "null buffer (grid, slots)");
+    if (!h_ls && !y) return fail(LDPC5G_ESIZE, "null buffer: both h_ls and y are NULL, nothing to do");
+    const size_t al = in_dtype == LDPC5G_F64 ? 16 : 8;
+    if (!aligned(grid, al) || !aligned(h_ls, al) || !aligned(y, al) || !aligned(slots, 4))
+        return fail(LDPC5G_ESIZE, "a buffer is not aligned to its element size");
+    hipStream_t st = (hipStream_t)stream;
+    if (in_dtype == LDPC5G_F32) return launch_frontend<float2>(grid, ldgrid, slots, T, c, q, Nr, Nt, h_ls, ldh, y, ldy, st);
+    return launch_frontend<double2>(grid, ldgrid, slots, T, c, q, Nr, Nt, h_ls, ldh, y, ldy, st);
+}
+
+// the antenna, size, stride, null and alignment checks of a map call, then its launch;
+// precoding: [num_ant][NL] complex64 as float pairs, or null for identity
+template <typename Seq>
+int run_map(const SlotDmrs& c, const Seq& q, const void* sym, int64_t ldsym, const int32_t* re_idx, int64_t nre,
+            const int32_t* slots, int32_t T, int32_t num_ant, int32_t NL, const float* precoding, void* grid,
+            int64_t ldgrid, void* stream) {
+    if (num_ant != 1 && num_ant != 2 && num_ant != 4) return fail(LDPC5G_ESIZE, "num_ant=%d: supported num_ant in {1, 2, 4}", num_ant);
+    if (!precoding && NL > num_ant) return fail(LDPC5G_ESIZE, "NL=%d > num_ant=%d needs a precoding matrix", NL, num_ant);
+    if (nre < 0 || nre > (int64_t)kSlotSyms * 12 * c.rb_size) return fail(LDPC5G_ESIZE, "nre=%lld outside 0..14*12*rb_size", (long long)nre);
+    if (ldgrid < (int64_t)num_ant * kSlotSyms * c.carrier_re)
+        return fail(LDPC5G_ESIZE, "grid stride %lld shorter than num_ant*14*carrier_re", (long long)ldgrid);
+    if (nre > 0 && ldsym < nre * NL) return fail(LDPC5G_ESIZE, "sym stride %lld shorter than nre*NL", (long long)ldsym);
+    if (!grid || !slots || (nre > 0 && (!sym || !re_idx))) return fail(LDPC5G_ESIZE, "null buffer (sym, re_idx, slots, grid)");
+    if (!aligned(grid, 8) || !aligned(sym, 8) || !aligned(re_idx, 4) || !aligned(slots, 4))
+        return fail(LDPC5G_ESIZE, "a buffer is not aligned to its element size");
+    SlotPrecode P{};
+    P.identity = precoding ? 0 : 1;
+    if (precoding)
+        for (int a = 0; a < num_ant; ++a)
+            for (int l = 0; l < NL; ++l) P.w[a][l] = make_float2(precoding[2 * (a * NL + l)], precoding[2 * (a * NL + l) + 1]);
+    const int64_t N = 3 * (int64_t)c.rb_size;
+    const int64_t wide = nre > N ? nre : N;
+    const dim3 g((unsigned)((wide + kSlotThreads - 1) / kSlotThreads), 1 + c.S, T), b(kSlotThreads);
+    const int ld16 = aligned(sym, 16) && ldsym % 2 == 0;
+#define LDPC5G_MAP(NA, NL_)                                                                                           \
+    hipLaunchKernelGGL((slot_map_kernel<NA, NL_, Seq>), g, b, 0, (hipStream_t)stream, (const float2*)sym, ldsym, re_idx, \
+                       nre, slots, c, q, P, (float2*)grid, ldgrid, ld16)
+#define LDPC5G_MAP_NL(NA)                            \
+    if constexpr (Seq::kOneLayer) LDPC5G_MAP(NA, 1); \
+    else switch (NL) {                               \
+        case 1: LDPC5G_MAP(NA, 1); break;            \
+        case 2: LDPC5G_MAP(NA, 2); break;            \
+        case 3: LDPC5G_MAP(NA, 3); break;            \
+        default: LDPC5G_MAP(NA, 4); break;           \
     }
+    if (num_ant == 1) { LDPC5G_MAP_NL(1) } else if (num_ant == 2) { LDPC5G_MAP_NL(2) } else { LDPC5G_MAP_NL(4) }
+#undef LDPC5G_MAP_NL
 #undef LDPC5G_MAP
+    return check_hip(hipGetLastError(), "slot_map_kernel launch");
 }
 
 }  // namespace
@@ -335,32 +486,20 @@ int ldpc5g_slot_rx_frontend(const void* grid, int64_t ldgrid, int32_t in_dtype, 
                             int32_t nSCID, int32_t num_cdm_groups, void* h_ls, int64_t ldh, void* y, int64_t ldy,
                             void* stream) {
     clear_error();
-    if (in_dtype != LDPC5G_F32 && in_dtype != LDPC5G_F64) return fail(LDPC5G_ESIZE, "bad grid dtype %d", in_dtype);
-    if (Nr != 1 && Nr != 2 && Nr != 4) return fail(LDPC5G_ESIZE, "Nr=%d: supported Nr in {1, 2, 4}", Nr);
     if (Nt < 1 || Nt > 4) return fail(LDPC5G_ESIZE, "Nt=%d outside 1..4", Nt);
     if (!ports) return fail(LDPC5G_ESIZE, "ports is null");
     SlotDmrs c{};
+    GoldSeq q{};
     for (int p = 0; p < Nt; ++p) {
         if (ports[p] < 0 || ports[p] > 3) return fail(LDPC5G_ESIZE, "ports[%d]=%d: port 1000..1003 as 0..3", p, ports[p]);
         for (int o = 0; o < p; ++o)
             if (ports[o] == ports[p]) return fail(LDPC5G_ESIZE, "ports[%d]=%d repeats ports[%d]", p, ports[p], o);
         c.port[p] = ports[p];
     }
-    const int rc = check_dmrs(c, T, carrier_re, rb_start, rb_size, S, sym_idx, nNIDnSCID, nSCID, num_cdm_groups);
+    int rc = check_dmrs(c, T, carrier_re, rb_start, rb_size, S, sym_idx);
+    if (!rc) rc = check_gold(c, q, nNIDnSCID, nSCID, num_cdm_groups);
     if (rc) return rc;
-    const int64_t N = 3 * (int64_t)rb_size;
-    if (ldgrid < (int64_t)Nr * kSlotSyms * carrier_re)
-        return fail(LDPC5G_ESIZE, "grid stride %lld shorter than Nr*14*carrier_re", (long long)ldgrid);
-    if (h_ls && ldh < S * N * Nr * Nt) return fail(LDPC5G_ESIZE, "h_ls stride %lld shorter than S*N*Nr*Nt", (long long)ldh);
-    if (y && ldy < kSlotSyms * 4 * N * Nr) return fail(LDPC5G_ESIZE, "y stride %lld shorter than 14*12*rb_size*Nr", (long long)ldy);
-    if (!grid || !slots) return fail(LDPC5G_ESIZE, "null buffer (grid, slots)");
-    if (!h_ls && !y) return fail(LDPC5G_ESIZE, "null buffer: both h_ls and y are NULL, nothing to do");
-    const size_t al = in_dtype == LDPC5G_F64 ? 16 : 8;
-    if (!aligned(grid, al) || !aligned(h_ls, al) || !aligned(y, al) || !aligned(slots, 4))
-        return fail(LDPC5G_ESIZE, "a buffer is not aligned to its element size");
-    hipStream_t st = (hipStream_t)stream;
-    if (in_dtype == LDPC5G_F32) return launch_frontend<float2>(grid, ldgrid, slots, T, c, Nr, Nt, h_ls, ldh, y, ldy, st);
-    return launch_frontend<double2>(grid, ldgrid, slots, T, c, Nr, Nt, h_ls, ldh, y, ldy, st);
+    return run_frontend(c, q, grid, ldgrid, in_dtype, slots, T, Nr, Nt, h_ls, ldh, y, ldy, stream);
 }
 
 int ldpc5g_slot_map(const void* sym, int64_t ldsym, const int32_t* re_idx, int64_t nre, const int32_t* slots,
@@ -368,36 +507,39 @@ int ldpc5g_slot_map(const void* sym, int64_t ldsym, const int32_t* re_idx, int64
                     const float* precoding, int32_t S, const int32_t* sym_idx, int32_t nNIDnSCID, int32_t nSCID,
                     int32_t num_cdm_groups, void* grid, int64_t ldgrid, void* stream) {
     clear_error();
-    if (num_ant != 1 && num_ant != 2 && num_ant != 4) return fail(LDPC5G_ESIZE, "num_ant=%d: supported num_ant in {1, 2, 4}", num_ant);
     if (NL < 1 || NL > 4) return fail(LDPC5G_ESIZE, "NL=%d outside 1..4", NL);
-    if (!precoding && NL > num_ant) return fail(LDPC5G_ESIZE, "NL=%d > num_ant=%d needs a precoding matrix", NL, num_ant);
     SlotDmrs c{};
-    for (int l = 0; l < NL; ++l) c.port[l] = l;   // row l of the reference's map is port 1000 + l
-    const int rc = check_dmrs(c, T, carrier_re, rb_start, rb_size, S, sym_idx, nNIDnSCID, nSCID, num_cdm_groups);
+    GoldSeq q{};
+    int rc = check_dmrs(c, T, carrier_re, rb_start, rb_size, S, sym_idx);
+    if (!rc) rc = check_gold(c, q, nNIDnSCID, nSCID, num_cdm_groups);
     if (rc) return rc;
-    if (nre < 0 || nre > (int64_t)kSlotSyms * 12 * rb_size) return fail(LDPC5G_ESIZE, "nre=%lld outside 0..14*12*rb_size", (long long)nre);
-    if (ldgrid < (int64_t)num_ant * kSlotSyms * carrier_re)
-        return fail(LDPC5G_ESIZE, "grid stride %lld shorter than num_ant*14*carrier_re", (long long)ldgrid);
-    if (nre > 0 && ldsym < nre * NL) return fail(LDPC5G_ESIZE, "sym stride %lld shorter than nre*NL", (long long)ldsym);
-    if (!grid || !slots || (nre > 0 && (!sym || !re_idx))) return fail(LDPC5G_ESIZE, "null buffer (sym, re_idx, slots, grid)");
-    if (!aligned(grid, 8) || !aligned(sym, 8) || !aligned(re_idx, 4) || !aligned(slots, 4))
-        return fail(LDPC5G_ESIZE, "a buffer is not aligned to its element size");
-    SlotPrecode P{};
-    P.identity = precoding ? 0 : 1;
-    if (precoding)
-        for (int a = 0; a < num_ant; ++a)
-            for (int l = 0; l < NL; ++l) P.w[a][l] = make_float2(precoding[2 * (a * NL + l)], precoding[2 * (a * NL + l) + 1]);
-    const int64_t N = 3 * (int64_t)rb_size;
-    const int64_t wide = nre > N ? nre : N;
-    const dim3 g((unsigned)((wide + kSlotThreads - 1) / kSlotThreads), 1 + S, T);
-    const int ld16 = aligned(sym, 16) && ldsym % 2 == 0;
-    hipStream_t st = (hipStream_t)stream;
-    const float2* s2 = (const float2*)sym;
-    float2* g2 = (float2*)grid;
-    if (num_ant == 1) launch_map_na<1>(NL, g, st, s2, ldsym, re_idx, nre, slots, c, P, g2, ldgrid, ld16);
-    else if (num_ant == 2) launch_map_na<2>(NL, g, st, s2, ldsym, re_idx, nre, slots, c, P, g2, ldgrid, ld16);
-    else launch_map_na<4>(NL, g, st, s2, ldsym, re_idx, nre, slots, c, P, g2, ldgrid, ld16);
-    return check_hip(hipGetLastError(), "slot_map_kernel launch");
+    return run_map(c, q, sym, ldsym, re_idx, nre, slots, T, num_ant, NL, precoding, grid, ldgrid, stream);
+}
+
+int ldpc5g_slot_rx_frontend_tp(const void* grid, int64_t ldgrid, int32_t in_dtype, const int32_t* slots, int32_t T,
+                               int32_t carrier_re, int32_t rb_start, int32_t rb_size, int32_t Nr, int32_t port,
+                               int32_t S, const int32_t* sym_idx, int32_t nPuschID, int32_t hopping,
+                               const void* base_seq, void* h_ls, int64_t ldh, void* y, int64_t ldy, void* stream) {
+    clear_error();
+    SlotDmrs c{};
+    LowPaprSeq q{};
+    int rc = check_dmrs(c, T, carrier_re, rb_start, rb_size, S, sym_idx);
+    if (!rc) rc = check_low_papr(c, q, port, nPuschID, hopping, base_seq);
+    if (rc) return rc;
+    return run_frontend(c, q, grid, ldgrid, in_dtype, slots, T, Nr, 1, h_ls, ldh, y, ldy, stream);
+}
+
+int ldpc5g_slot_map_tp(const void* sym, int64_t ldsym, const int32_t* re_idx, int64_t nre, const int32_t* slots,
+                       int32_t T, int32_t carrier_re, int32_t rb_start, int32_t rb_size, int32_t num_ant, int32_t port,
+                       const float* precoding, int32_t S, const int32_t* sym_idx, int32_t nPuschID, int32_t hopping,
+                       const void* base_seq, void* grid, int64_t ldgrid, void* stream) {
+    clear_error();
+    SlotDmrs c{};
+    LowPaprSeq q{};
+    int rc = check_dmrs(c, T, carrier_re, rb_start, rb_size, S, sym_idx);
+    if (!rc) rc = check_low_papr(c, q, port, nPuschID, hopping, base_seq);
+    if (rc) return rc;
+    return run_map(c, q, sym, ldsym, re_idx, nre, slots, T, num_ant, 1, precoding, grid, ldgrid, stream);
 }
 
 }  // extern "C"

@@ -378,8 +378,39 @@ def slot_data_re_idx_device(pdsch_config, device):
     return t.from_numpy(slot_data_re_idx(pdsch_config)[0]).to(device)
 
 
-def _ld(x, T, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
-    return x.stride(0) if T > 1 else row
+def _st(x, d, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
+    return x.stride(d) if x.shape[d] > 1 else row
+
+
+def _optr(x):
+    return _lib.ptr(x) if x is not None else None
+
+
+def _frontend(grid, slots, want, params, entry, seq_args):
+    """What slot_frontend and pusch_tp_frontend share.  params(): the configuration's fields after
+    the asserts and refusals that come before any GPU work; entry: the library call; seq_args(p, T,
+    S, dev): its arguments between Nr and S and between sym_idx and h_ls (the DMRS sequence's)."""
+    assert want and all(w in ("h_ls", "y") for w in want), f"want {want!r}: a selection of 'h_ls', 'y'"
+    p = params()
+    t = _lib.require_gpu()
+    assert grid.dim() == 3 and grid.dtype in (t.complex64, t.complex128) and grid[0].is_contiguous(), \
+        "grid: (T, Nr, 14*carrier_re) complex, only the slot stride is free"
+    T, Nr, W = grid.shape
+    assert W % 14 == 0, f"grid rows of {W} elements are not 14 symbols"
+    assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == grid.device
+    S, N, NL = len(p["symlist"]), 3 * p["rb_size"], p["NL"]
+    dev = grid.device
+    first, rest = seq_args(p, T, S, dev)
+    h_ls = t.empty((T, S, N, Nr, NL), dtype=grid.dtype, device=dev) if "h_ls" in want else None
+    y = t.empty((T, 14 * 4 * N, Nr), dtype=grid.dtype, device=dev) if "y" in want else None
+    syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
+    with t.cuda.device(dev):
+        _lib.check(getattr(_lib.lib(), entry)(
+            _lib.ptr(grid), _st(grid, 0, Nr * W), _lib.F32 if grid.dtype == t.complex64 else _lib.F64,
+            _lib.ptr(slots), T, W // 14, p["rb_start"], p["rb_size"], Nr, *first, S, syms, *rest,
+            _optr(h_ls), S * N * Nr * NL, _optr(y), 14 * 4 * N * Nr, _lib.stream_ptr(dev)))
+    outs = {"h_ls": h_ls, "y": y}
+    return tuple(outs[w] for w in want)
 
 
 def slot_frontend(grid, slots, pdsch_config, want=("h_ls", "y")):
@@ -391,28 +422,45 @@ def slot_frontend(grid, slots, pdsch_config, want=("h_ls", "y")):
     slot numbers; pdsch_config: the reference's pdsch_config (or pusch_config) dict.  Returns, in
     the order of `want`, a tuple of h_ls (T, S, 3*RBSize, Nr, NL) — channel_estimate's input — and
     y (T, 14*12*RBSize, Nr) — the allocation's PRBs of all 14 symbols, interleaved — of grid's dtype."""
-    assert want and all(w in ("h_ls", "y") for w in want), f"want {want!r}: a selection of 'h_ls', 'y'"
-    p = _slot_params(pdsch_config)   # the reference's asserts and refusals come before any GPU work
-    t = _lib.require_gpu()
-    assert grid.dim() == 3 and grid.dtype in (t.complex64, t.complex128) and grid[0].is_contiguous(), \
-        "grid: (T, Nr, 14*carrier_re) complex, only the slot stride is free"
-    T, Nr, W = grid.shape
-    assert W % 14 == 0, f"grid rows of {W} elements are not 14 symbols"
-    assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == grid.device
-    S, N, NL = len(p["symlist"]), 3 * p["rb_size"], p["NL"]
-    dev = grid.device
-    h_ls = t.empty((T, S, N, Nr, NL), dtype=grid.dtype, device=dev) if "h_ls" in want else None
-    y = t.empty((T, 14 * 4 * N, Nr), dtype=grid.dtype, device=dev) if "y" in want else None
-    ports = (_lib.ctypes.c_int32 * 4)(*[q - 1000 for q in p["ports"]])
+    def seq_args(p, T, S, dev):
+        ports = (_lib.ctypes.c_int32 * 4)(*[q - 1000 for q in p["ports"]])
+        return (p["NL"], ports), (p["nid"], p["nscid"], p["cdm"])
+    return _frontend(grid, slots, want, lambda: _slot_params(pdsch_config), "ldpc5g_slot_rx_frontend", seq_args)
+
+
+def _map(t, sym, slots, p, carrier_prbs, num_ant, precoding, out, re_idx, entry, seq_args):
+    """What slot_map and pusch_tp_map share, after their parameter extraction.  re_idx: the
+    device tensor; entry: the library call; seq_args(T, S, dev): its argument between num_ant and
+    precoding, those between sym_idx and grid (the DMRS sequence's), and what becomes of sym on its
+    way into the call."""
+    import numpy as np
+    NL, dev, num_ant = p["NL"], sym.device, int(num_ant)
+    assert re_idx.dim() == 1 and re_idx.dtype == t.int32 and re_idx.is_contiguous() and re_idx.device == dev
+    nre = re_idx.shape[0]
+    assert sym.dim() == 2 and sym.dtype == t.complex64 and sym.stride(1) == 1
+    T = sym.shape[0]
+    assert sym.shape[1] == nre * NL, f"sym has {sym.shape[1]} symbols per slot, the allocation holds nre*NL = {nre}*{NL}"
+    assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == dev
+    W = 14 * 12 * int(carrier_prbs)
+    if out is None:
+        out = t.zeros((T, num_ant, W), dtype=t.complex64, device=dev)
+    assert out.dtype == t.complex64 and out.shape == (T, num_ant, W) and out[0].is_contiguous() and out.device == dev
+    pm = None
+    if precoding is not None:
+        w = np.asarray(precoding, np.complex64)
+        w = np.ascontiguousarray((w.reshape(-1, 1) if NL == 1 else w)[:num_ant, :NL])
+        assert w.shape == (num_ant, NL), f"precoding {w.shape}: (num_ant, NL) = ({num_ant}, {NL}) wanted"
+        pm = w.view(np.float32).ctypes.data_as(_lib.ctypes.c_void_p)
+    S = len(p["symlist"])
+    first, rest, prepare = seq_args(T, S, dev)
+    sym = prepare(sym)
     syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
     with t.cuda.device(dev):
-        _lib.check(_lib.lib().ldpc5g_slot_rx_frontend(
-            _lib.ptr(grid), _ld(grid, T, Nr * W), _lib.F32 if grid.dtype == t.complex64 else _lib.F64,
-            _lib.ptr(slots), T, W // 14, p["rb_start"], p["rb_size"], Nr, NL, ports, S, syms, p["nid"], p["nscid"],
-            p["cdm"], _lib.ptr(h_ls) if h_ls is not None else None, S * N * Nr * NL,
-            _lib.ptr(y) if y is not None else None, 14 * 4 * N * Nr, _lib.stream_ptr(dev)))
-    outs = {"h_ls": h_ls, "y": y}
-    return tuple(outs[w] for w in want)
+        _lib.check(getattr(_lib.lib(), entry)(
+            _lib.ptr(sym), _st(sym, 0, nre * NL), _lib.ptr(re_idx), nre, _lib.ptr(slots), T, W // 14,
+            p["rb_start"], p["rb_size"], num_ant, first, pm, S, syms, *rest,
+            _lib.ptr(out), _st(out, 0, num_ant * W), _lib.stream_ptr(dev)))
+    return out
 
 
 def slot_map(sym, slots, pdsch_config, carrier_prbs, num_ant, precoding=None, out=None, re_idx=None):
@@ -424,38 +472,15 @@ def slot_map(sym, slots, pdsch_config, carrier_prbs, num_ant, precoding=None, ou
     1000 .. 1000 + NL - 1 in order; re_idx: slot_data_re_idx_device's tensor, to save its upload.
     Writes DMRS and data into out (T, num_ant, 14*12*carrier_prbs)
     complex64 — every other RE is left as it is — or into a new zeroed grid, and returns it."""
-    import numpy as np
     p = _slot_params(pdsch_config)
     t = _lib.require_gpu()
     NL = p["NL"]
     assert p["ports"] == [1000 + l for l in range(NL)], \
         f"PortIndexList {p['ports']}: the transmit map needs ports 1000..{999 + NL} in order (nr_pdsch_dmrs.py:81-84)"
-    dev = sym.device
     if re_idx is None:
-        re_idx = slot_data_re_idx_device(pdsch_config, dev)
-    assert re_idx.dim() == 1 and re_idx.dtype == t.int32 and re_idx.is_contiguous() and re_idx.device == dev
-    nre = re_idx.shape[0]
-    assert sym.dim() == 2 and sym.dtype == t.complex64 and sym.stride(1) == 1
-    T = sym.shape[0]
-    assert sym.shape[1] == nre * NL, f"sym has {sym.shape[1]} symbols per slot, the allocation holds nre*NL = {nre}*{NL}"
-    assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == dev
-    W = 14 * 12 * int(carrier_prbs)
-    if out is None:
-        out = t.zeros((T, int(num_ant), W), dtype=t.complex64, device=dev)
-    assert out.dtype == t.complex64 and out.shape == (T, int(num_ant), W) and out[0].is_contiguous() and out.device == dev
-    pm = None
-    if precoding is not None:
-        w = np.ascontiguousarray(np.asarray(precoding, np.complex64)[:int(num_ant), :NL])
-        assert w.shape == (int(num_ant), NL), f"precoding {w.shape}: (num_ant, NL) wanted"
-        pm = w.view(np.float32).ctypes.data_as(_lib.ctypes.c_void_p)
-    S = len(p["symlist"])
-    syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
-    with t.cuda.device(dev):
-        _lib.check(_lib.lib().ldpc5g_slot_map(
-            _lib.ptr(sym), _ld(sym, T, nre * NL), _lib.ptr(re_idx), nre, _lib.ptr(slots), T, W // 14,
-            p["rb_start"], p["rb_size"], int(num_ant), NL, pm, S, syms, p["nid"], p["nscid"], p["cdm"],
-            _lib.ptr(out), _ld(out, T, int(num_ant) * W), _lib.stream_ptr(dev)))
-    return out
+        re_idx = slot_data_re_idx_device(pdsch_config, sym.device)
+    return _map(t, sym, slots, p, carrier_prbs, num_ant, precoding, out, re_idx, "ldpc5g_slot_map",
+                lambda T, S, dev: (NL, (p["nid"], p["nscid"], p["cdm"]), lambda x: x))
 
 
 # ------------------------------------------------------------------ PUSCH transform precoding
@@ -498,7 +523,7 @@ def transform_precode(x, rb_size, inverse=False, out=None):
     assert out.dtype == x.dtype and out.shape == (T, W) and out.stride(1) == 1 and out.device == x.device
     with t.cuda.device(x.device):
         _lib.check(_lib.lib().ldpc5g_transform_precode(
-            _lib.ptr(x), _ld(x, T, W), _lib.ptr(out), _ld(out, T, W),
+            _lib.ptr(x), _st(x, 0, W), _lib.ptr(out), _st(out, 0, W),
             _lib.F32 if x.dtype == t.complex64 else _lib.F64, T, W // M, int(rb_size), 1 if inverse else 0,
             _lib.stream_ptr(x.device)))
     return out
@@ -582,6 +607,12 @@ def _tp_base_seq(base_seq, T, S, MZC, dev):
     return base_seq
 
 
+def _tp_seq_args(p, base_seq, T, S, dev):
+    """(port, (nPuschID, hopping, base_seq)) of the two _tp library calls"""
+    bs = _tp_base_seq(base_seq, T, S, 6 * p["rb_size"], dev)
+    return p["ports"][0] - 1000, (p["npuschid"], p["hopping"], _optr(bs))
+
+
 def pusch_tp_frontend(grid, slots, pusch_config, want=("h_ls", "y"), base_seq=None):
     """slot_frontend for a pusch_config with nTransPrecode = 1 (ldpc5g_slot_rx_frontend_tp;
     pusch_dmrs_LS_est, nr_pusch_dmrs.py:107-200 with the low-PAPR sequence of :216-249, its group /
@@ -589,29 +620,11 @@ def pusch_tp_frontend(grid, slots, pusch_config, want=("h_ls", "y"), base_seq=No
     base_seq: the DMRS base sequences, (S, 6*RBSize) or (T, S, 6*RBSize) complex128 (host array or
     device tensor), instead of the generated ones; needed for RBSize <= 4.  Returns, in the order of
     `want`, h_ls (T, S, 3*RBSize, Nr, 1) and y (T, 14*12*RBSize, Nr) of grid's dtype."""
-    assert want and all(w in ("h_ls", "y") for w in want), f"want {want!r}: a selection of 'h_ls', 'y'"
-    p = _tp_params(pusch_config, base_seq)   # asserts and refusals come before any GPU work
-    t = _lib.require_gpu()
-    assert grid.dim() == 3 and grid.dtype in (t.complex64, t.complex128) and grid[0].is_contiguous(), \
-        "grid: (T, Nr, 14*carrier_re) complex, only the slot stride is free"
-    T, Nr, W = grid.shape
-    assert W % 14 == 0, f"grid rows of {W} elements are not 14 symbols"
-    assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == grid.device
-    S, N = len(p["symlist"]), 3 * p["rb_size"]
-    dev = grid.device
-    bs = _tp_base_seq(base_seq, T, S, 2 * N, dev)
-    h_ls = t.empty((T, S, N, Nr, 1), dtype=grid.dtype, device=dev) if "h_ls" in want else None
-    y = t.empty((T, 14 * 4 * N, Nr), dtype=grid.dtype, device=dev) if "y" in want else None
-    syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
-    with t.cuda.device(dev):
-        _lib.check(_lib.lib().ldpc5g_slot_rx_frontend_tp(
-            _lib.ptr(grid), _ld(grid, T, Nr * W), _lib.F32 if grid.dtype == t.complex64 else _lib.F64,
-            _lib.ptr(slots), T, W // 14, p["rb_start"], p["rb_size"], Nr, p["ports"][0] - 1000, S, syms,
-            p["npuschid"], p["hopping"], _lib.ptr(bs) if bs is not None else None,
-            _lib.ptr(h_ls) if h_ls is not None else None, S * N * Nr,
-            _lib.ptr(y) if y is not None else None, 14 * 4 * N * Nr, _lib.stream_ptr(dev)))
-    outs = {"h_ls": h_ls, "y": y}
-    return tuple(outs[w] for w in want)
+    def seq_args(p, T, S, dev):
+        port, rest = _tp_seq_args(p, base_seq, T, S, dev)
+        return (port,), rest
+    return _frontend(grid, slots, want, lambda: _tp_params(pusch_config, base_seq), "ldpc5g_slot_rx_frontend_tp",
+                     seq_args)
 
 
 def pusch_tp_map(sym, slots, pusch_config, carrier_prbs, num_ant, precoding=None, out=None, re_idx=None,
@@ -623,38 +636,12 @@ def pusch_tp_map(sym, slots, pusch_config, carrier_prbs, num_ant, precoding=None
     symbols of 12*RBSize; precoding: (num_ant, 1) array-like or None (antenna 0 carries the layer);
     the layer's port is PortIndexList[0]; base_seq as pusch_tp_frontend.  Returns the grid
     (T, num_ant, 14*12*carrier_prbs) complex64 (out, or a new zeroed one)."""
-    import numpy as np
     p = _tp_params(pusch_config, base_seq)
     t = _lib.require_gpu()
-    dev = sym.device
     if re_idx is None:
-        re_idx = t.from_numpy(pusch_tp_data_re_idx(pusch_config)[0]).to(dev)
-    assert re_idx.dim() == 1 and re_idx.dtype == t.int32 and re_idx.is_contiguous() and re_idx.device == dev
-    nre = re_idx.shape[0]
-    assert sym.dim() == 2 and sym.dtype == t.complex64 and sym.stride(1) == 1
-    T = sym.shape[0]
-    assert sym.shape[1] == nre, f"sym has {sym.shape[1]} symbols per slot, the allocation holds nre = {nre}"
-    assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == dev
-    W = 14 * 12 * int(carrier_prbs)
-    if out is None:
-        out = t.zeros((T, int(num_ant), W), dtype=t.complex64, device=dev)
-    assert out.dtype == t.complex64 and out.shape == (T, int(num_ant), W) and out[0].is_contiguous() and out.device == dev
-    pm = None
-    if precoding is not None:
-        w = np.ascontiguousarray(np.asarray(precoding, np.complex64).reshape(-1, 1)[:int(num_ant)])
-        assert w.shape == (int(num_ant), 1), f"precoding {w.shape}: (num_ant, 1) wanted"
-        pm = w.view(np.float32).ctypes.data_as(_lib.ctypes.c_void_p)
-    S, N = len(p["symlist"]), 3 * p["rb_size"]
-    bs = _tp_base_seq(base_seq, T, S, 2 * N, dev)
-    spread = transform_precode(sym, p["rb_size"])
-    syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
-    with t.cuda.device(dev):
-        _lib.check(_lib.lib().ldpc5g_slot_map_tp(
-            _lib.ptr(spread), _ld(spread, T, nre), _lib.ptr(re_idx), nre, _lib.ptr(slots), T, W // 14,
-            p["rb_start"], p["rb_size"], int(num_ant), p["ports"][0] - 1000, pm, S, syms, p["npuschid"],
-            p["hopping"], _lib.ptr(bs) if bs is not None else None, _lib.ptr(out), _ld(out, T, int(num_ant) * W),
-            _lib.stream_ptr(dev)))
-    return out
+        re_idx = t.from_numpy(pusch_tp_data_re_idx(pusch_config)[0]).to(sym.device)
+    return _map(t, sym, slots, p, carrier_prbs, num_ant, precoding, out, re_idx, "ldpc5g_slot_map_tp",
+                lambda T, S, dev: (*_tp_seq_args(p, base_seq, T, S, dev), lambda x: transform_precode(x, p["rb_size"])))
 
 
 # ------------------------------------------------------------------ OFDM low-PHY
@@ -692,10 +679,6 @@ def _ofdm_check(t, x, name, W, other):
     if other is not None:
         assert other.dtype == x.dtype and other.device == x.device and other.shape[:2] == x.shape[:2], \
             f"out: dtype, device and (T, Nr) of {name}"
-
-
-def _st(x, d, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
-    return x.stride(d) if x.shape[d] > 1 else row
 
 
 def ofdm_demod(td, scs, carrier_prbs, carrier_frequency_in_mhz=0, out=None):

@@ -427,6 +427,25 @@ def sch_ce_ml_rx_batch(y, h_ls, ce, algo, re_idx, mod, cfg, L, **kw):
     return sch_ml_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, **kw)
 
 
+def _slot_chain_params(pdsch_config, algo):
+    """sch_slot_rx_batch's refusals, which come before any GPU work; phy._slot_params' fields."""
+    from . import phy
+    assert algo in _lib.EQ_ALGO or algo in _lib.ML_ALGO, \
+        f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO) + sorted(_lib.ML_ALGO)}"
+    return phy._slot_params(pdsch_config)
+
+
+def _tp_chain_params(pusch_config, algo, base_seq):
+    """sch_pusch_tp_rx_batch's refusals, which come before any GPU work; phy._tp_params' fields."""
+    from . import phy
+    if algo in _lib.ML_ALGO:
+        raise NotImplementedError(f"algo {algo!r}: with transform precoding the reference demodulates after the "
+                                  "de-spreading IDFT and throws the ML detectors' LLRs away (nr_pusch.py:178-194); "
+                                  f"use one of {sorted(_lib.EQ_ALGO)}")
+    assert algo in _lib.EQ_ALGO, f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO)}"
+    return phy._tp_params(pusch_config, base_seq)
+
+
 def sch_slot_rx_batch(grid, slots, pdsch_config, ce, algo, mod, cfg, L, re_idx=None, **kw):
     """The reference's receiver from the slot grid to the transport block — Pdsch.H_LS_est,
     NrChannelEstimation.channel_est and Pdsch.RX_process (nr_pdsch.py:212-284, 345-352) — for T
@@ -439,12 +458,10 @@ def sch_slot_rx_batch(grid, slots, pdsch_config, ce, algo, mod, cfg, L, re_idx=N
     (uploaded here, once per call, when it is not given).  The data REs (phy.slot_data_re_idx) must
     carry exactly the transport block: nre * NL * Qm == cfg.G."""
     from . import phy
-    assert algo in _lib.EQ_ALGO or algo in _lib.ML_ALGO, \
-        f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO) + sorted(_lib.ML_ALGO)}"
+    p = _slot_chain_params(pdsch_config, algo)
     h_ls, y = phy.slot_frontend(grid, slots, pdsch_config)
     if re_idx is None:
         re_idx = phy.slot_data_re_idx_device(pdsch_config, grid.device)
-    p = phy._slot_params(pdsch_config)
     ce = dict(ce, sym_map=p["symlist"], num_cdm_groups=p["cdm"])
     y, h, cov = _ce_stage(y, h_ls, ce)
     if algo in _lib.EQ_ALGO:
@@ -463,12 +480,7 @@ def sch_pusch_tp_rx_batch(grid, slots, pusch_config, ce, algo, mod, cfg, L, re_i
     re_idx: the device tensor of phy.pusch_tp_data_re_idx(pusch_config)[0] (uploaded here when not
     given); base_seq as phy.pusch_tp_frontend; everything else as sch_slot_rx_batch."""
     from . import phy
-    if algo in _lib.ML_ALGO:
-        raise NotImplementedError(f"algo {algo!r}: with transform precoding the reference demodulates after the "
-                                  "de-spreading IDFT and throws the ML detectors' LLRs away (nr_pusch.py:178-194); "
-                                  f"use one of {sorted(_lib.EQ_ALGO)}")
-    assert algo in _lib.EQ_ALGO, f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO)}"
-    p = phy._tp_params(pusch_config, base_seq)   # asserts and refusals come before any GPU work
+    p = _tp_chain_params(pusch_config, algo, base_seq)
     h_ls, y = phy.pusch_tp_frontend(grid, slots, pusch_config, base_seq=base_seq)
     t = _lib.torch()
     if re_idx is None:
@@ -495,15 +507,10 @@ def sch_td_rx_batch(td, slots, config, carrier, ce, algo, mod, cfg, L, **kw):
     scs = carrier["scs"]
     prbs = nr_slot.get_carrier_prb_size(scs, carrier["BW"])
     tp = config.get("nTransPrecode", 0) == 1
-    # the chain's own refusals come before any GPU work
-    if tp:
-        if algo in _lib.ML_ALGO:
-            raise NotImplementedError(f"algo {algo!r}: refused with transform precoding, use one of {sorted(_lib.EQ_ALGO)}")
-        phy._tp_params(config, kw.get("base_seq"))
+    if tp:   # the chain's own refusals come before any GPU work
+        _tp_chain_params(config, algo, kw.get("base_seq"))
     else:
-        assert algo in _lib.EQ_ALGO or algo in _lib.ML_ALGO, \
-            f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO) + sorted(_lib.ML_ALGO)}"
-        phy._slot_params(config)
+        _slot_chain_params(config, algo)
     grid = phy.ofdm_demod(td, scs, prbs, carrier.get("carrier_frequency_in_mhz", 0))
     chain = sch_pusch_tp_rx_batch if tp else sch_slot_rx_batch
     return chain(grid, slots, config, ce, algo, mod, cfg, L, **kw)

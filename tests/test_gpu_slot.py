@@ -172,6 +172,12 @@ def test_slot_map_against_the_restatement_and_the_reference(torch, phy, golden, 
             assert np.abs(got[t][written] - c["grid"][written]).max() <= tol
     fresh = phy.slot_map(torch.tensor(sym).cuda(), _slots(torch, *slots), cfg, PRB, num_ant, precoding=pm)
     assert np.abs(fresh[0].cpu().numpy() - c["grid"]).max() <= tol
+    if NL in (2, 4):   # rows an odd number of elements apart (not 16-byte aligned): the same bits
+        odd = torch.zeros((2, sym.shape[1] + 1), dtype=torch.complex64, device="cuda")[:, :sym.shape[1]]
+        odd.copy_(torch.tensor(sym))
+        assert odd.stride(0) % 2 == 1
+        again = phy.slot_map(odd, _slots(torch, *slots), cfg, PRB, num_ant, precoding=pm)
+        assert _same_bits(torch, again, fresh)
 
 
 @pytest.mark.parametrize("NL", [1, 2, 4])

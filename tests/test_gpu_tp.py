@@ -14,6 +14,8 @@ Bounds (relative to the largest magnitude of the reference array unless stated):
   transmit grid vs the reference's ..... the gap stored with the case (identity precoding), 4 2^-23
                                          max|grid| with a precoding matrix
 """
+import functools
+
 import numpy as np
 import pytest
 
@@ -232,6 +234,61 @@ def test_hopping_follows_the_slots_and_base_seq_equals_the_generated_path(torch,
     assert _same_bits(torch, h_b, h_ls)
 
 
+# RBSize 90 at RBStart 5 of a 96-PRB carrier: N = 270 DMRS REs per symbol, so a second workgroup whose
+# first wave has 14 live lanes and whose other three have none.  The recorded cases stop at N = 60.
+WIDE_PRB, WIDE_SLOTS = 96, (19, 0, 7)
+WIDE_PORT = {1: 1002, 2: 1001, 4: 1003}
+
+
+def _wide_cfg(**kw):
+    return tp_ref.pusch_config(rb_start=5, rb_size=90, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_ls(hopping, Nr):
+    """(config, grid (3, Nr, 14*12*96) of complex64 values, tp_ref's H_LS per slot), made once and read-only."""
+    cfg = _wide_cfg(port=WIDE_PORT[Nr], add_pos=3, hopping=hopping, npuschid=1007)
+    g = _rand(np.random.default_rng(90 + Nr), (3, Nr, 14 * 12 * WIDE_PRB), np.complex64)
+    refs = [tp_ref.ls_est(g[t], cfg, WIDE_SLOTS[t]) for t in range(3)]
+    for a in [g] + refs:
+        a.setflags(write=False)
+    return cfg, g, refs
+
+
+@pytest.mark.parametrize("dtype", [np.complex64, np.complex128])
+@pytest.mark.parametrize("Nr", [1, 2, 4])
+@pytest.mark.parametrize("hopping", ["groupHopping", "sequenceHopping"])
+def test_frontend_second_workgroup_and_unaligned_rows(torch, phy, hopping, Nr, dtype):
+    """T = 3, slots [19, 0, 7], the slot stride padded by 6 and by 7 elements (7: complex64 rows that
+    are not 16-byte aligned): h_ls equal to tp_ref per slot, y bit for bit slot_ref.extract, the batch
+    bit for bit the slots run one by one and the call handed the same sequences as base_seq."""
+    cfg, g, refs = _wide_ls(hopping, Nr)
+    p = tp_ref.tp_params(cfg)
+    S, W, MZC = len(p["syms"]), 14 * 12 * WIDE_PRB, 6 * 90
+    uv = [tp_ref.hop_uv(1007, hopping, MZC, s, sym) for s in WIDE_SLOTS for sym in p["syms"]]
+    assert len(set(uv)) > 1, "the case does not hop"
+    base = phy.low_papr_seq([a for a, _ in uv], [b for _, b in uv], MZC).view(3, S, MZC)
+    slots = _slots(torch, *WIDE_SLOTS)
+    want_y = [slot_ref.extract(g[t].astype(dtype), cfg) for t in range(3)]
+    for pad in (6, 7):
+        buf = torch.zeros((3, Nr * W + pad), dtype=torch.complex64 if dtype == np.complex64 else torch.complex128,
+                          device="cuda")
+        grid = buf[:, :Nr * W].view(3, Nr, W)
+        grid.copy_(torch.tensor(g.astype(dtype)))
+        assert grid.stride(0) == Nr * W + pad
+        h_ls, y = phy.pusch_tp_frontend(grid, slots, cfg)
+        assert h_ls.shape == (3, S, 270, Nr, 1) and y.shape == (3, 14 * 12 * 90, Nr) and h_ls.dtype == y.dtype == grid.dtype
+        for t in range(3):
+            err = _relmax(h_ls[t].cpu().numpy(), refs[t])
+            print(hopping, Nr, np.dtype(dtype).name, "pad", pad, "slot", WIDE_SLOTS[t], "h_ls vs tp_ref", err)
+            assert err <= (1e-12 if dtype == np.complex128 else 2.0 ** -22)
+            assert np.array_equal(y[t].cpu().numpy().view(np.uint8), want_y[t].view(np.uint8))
+            h1, y1 = phy.pusch_tp_frontend(grid[t:t + 1].contiguous(), _slots(torch, WIDE_SLOTS[t]), cfg)
+            assert _same_bits(torch, h1[0], h_ls[t]) and _same_bits(torch, y1[0], y[t])
+        (h_b,) = phy.pusch_tp_frontend(grid, slots, cfg, want=("h_ls",), base_seq=base)
+        assert _same_bits(torch, h_b, h_ls)
+
+
 # ------------------------------------------------------------------ the transmit side
 @pytest.mark.parametrize("name", sorted(tp_ref.MAP_CASES))
 def test_transmit_grid_and_process_equal_the_reference(torch, phy, golden, name):
@@ -261,6 +318,36 @@ def test_transmit_grid_and_process_equal_the_reference(torch, phy, golden, name)
             assert err <= tol
     fresh = phy.pusch_tp_map(torch.tensor(sym).cuda(), _slots(torch, *slots), cfg, PRB, num_ant, precoding=pm)
     assert np.abs(fresh[0].cpu().numpy() - c["grid"]).max() <= tol
+
+
+WIDE_PM = {1: None, 2: [0.5 + 0.5j, -0.5j], 4: [0.5, -0.5, 0.5j, 0]}   # a zero weight: signed zeros
+
+
+@pytest.mark.parametrize("num_ant", [1, 2, 4])
+@pytest.mark.parametrize("port", [1001, 1002])
+def test_transmit_grid_second_workgroup(torch, phy, port, num_ant):
+    """RBSize 90 on the 96-PRB carrier, T = 2, ports 1001 and 1002, one antenna without and two and
+    four with a precoding vector: the written REs equal tp_ref.tp_map, every other RE keeps the
+    sentinel (the other comb of the DMRS symbols included)."""
+    cfg = _wide_cfg(port=port, add_pos=1, hopping="groupHopping", npuschid=301)
+    pm = None if WIDE_PM[num_ant] is None else np.array(WIDE_PM[num_ant], np.complex64).reshape(-1, 1)
+    nre = len(phy.pusch_tp_data_re_idx(cfg)[0])
+    sym = _rand(np.random.default_rng(port + num_ant), (2, nre), np.complex64)
+    slots = [9, 10]
+    sentinel = np.complex64(7 - 3j)
+    W = 14 * 12 * WIDE_PRB
+    out = torch.full((2, num_ant, W), complex(sentinel), dtype=torch.complex64, device="cuda")
+    res = phy.pusch_tp_map(torch.tensor(sym).cuda(), _slots(torch, *slots), cfg, WIDE_PRB, num_ant, precoding=pm, out=out)
+    assert res is out
+    got = out.cpu().numpy()
+    for t in range(2):
+        ref = tp_ref.tp_map(sym[t], cfg, slots[t], WIDE_PRB, num_ant, pm, grid=np.full((num_ant, W), np.nan + 0j, np.complex64))
+        written = ~np.isnan(ref.real)
+        assert written.sum() == num_ant * (nre + 2 * 2 * 270)
+        assert np.all(got[t][~written] == sentinel), "an RE outside the map was written"
+        err, gmax = np.abs(got[t][written] - ref[written]).max(), float(np.abs(ref[written]).max())
+        print("port", port, "num_ant", num_ant, "slot", slots[t], "grid vs tp_ref", err, "tol", 4 * 2.0 ** -23 * gmax)
+        assert err <= 4 * 2.0 ** -23 * gmax
 
 
 def test_process_dropin(torch, golden):

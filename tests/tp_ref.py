@@ -1,4 +1,5 @@
-"""Float64 numpy restatement of PUSCH transform precoding (python_5gtoolbox_amd/csrc/ldpc5g_tp.hip):
+"""Float64 numpy restatement of PUSCH transform precoding (python_5gtoolbox_amd/csrc/ldpc5g_tp.hip and
+the low-PAPR DMRS source of ldpc5g_slot.hip):
 the spreading DFT and its inverse (py5gphy/nr_pusch/nr_pusch_process.py:39-54, nr_pusch.py:170-194),
 the low-PAPR sequence with the phase index reduced exactly in integers (common/lowPAPR_seq.py:5-41),
 the group / sequence hopping (nr_pusch_dmrs.py:216-249), and the LS estimate and transmit map that

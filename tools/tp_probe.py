@@ -3,9 +3,11 @@
 inverse, beside rocFFT on the same tensors (torch.fft.fft / ifft with norm="ortho" on the
 (T*12, M) view).  Each variant is event-timed on its own: warm-ups, then interleaved steps of every
 variant, each step REPS calls back to back (one launch is a few microseconds: the step time over
-REPS is the per-call time with the launch gaps the stream leaves), min / median / max.  Then the
-whole sch_pusch_tp_rx_batch call at RBSize 270, 1 x 4, beside sch_slot_rx_batch on the same
-allocation without transform precoding, in one interleaved loop.
+REPS is the per-call time with the launch gaps the stream leaves), min / median / max.  Then, at
+the chain's shape (RBSize 270 of 273, 1 x 4), ldpc5g_slot_rx_frontend_tp (its LS and extraction
+launches, each alone and both together) and ldpc5g_slot_map_tp, each call event-timed on its own as
+in tools/slot_probe.py, and the whole sch_pusch_tp_rx_batch call beside sch_slot_rx_batch on the
+same allocation without transform precoding, in one interleaved loop.
 
     python tools/tp_probe.py [--T 32] [--steps 20] [--warmup 3] [--out profiles/tp/probe.json]
 
@@ -22,6 +24,7 @@ and written once) over the time, as a fraction of the 6.29 TB/s copy ceiling (DE
 """
 import argparse
 import csv
+import ctypes
 import glob
 import json
 import os
@@ -234,21 +237,70 @@ def main():
         res["transform"][pname] = line
         for k, v in line.items():
             print(pname, k, json.dumps(v), flush=True)
-    if args.once:
-        return
 
-    # ---- the chain: RBSize 270, 1 x 4, with and without transform precoding
+    # ---- the low-PAPR front end and map at the chain's shape: the entry points themselves, one call per event pair
     cfg1, cfg0 = pusch_config(1), pusch_config(0)
     re_idx = torch.from_numpy(phy.pusch_tp_data_re_idx(cfg1)[0]).to(dev)
     assert torch.equal(re_idx, phy.slot_data_re_idx_device(cfg0, dev))
     nre, Qm = re_idx.numel(), 2
+    RB, S, W = 270, 2, 14 * 12 * CARRIER_PRB
+    syms = (ctypes.c_int32 * 4)(2, 11)
+    slots = (torch.arange(T, device=dev, dtype=torch.int32) % 20).contiguous()
+    spread = torch.complex(torch.randn((T, nre), dtype=torch.float32, device=dev, generator=gen),
+                           torch.randn((T, nre), dtype=torch.float32, device=dev, generator=gen))
+    grid_out = torch.zeros((T, 1, W), dtype=torch.complex64, device=dev)
+
+    def raw_map():
+        rc = lib.ldpc5g_slot_map_tp(_lib.ptr(spread), spread.stride(0), _lib.ptr(re_idx), nre, _lib.ptr(slots), T, W // 14,
+                                    0, RB, 1, 0, None, S, syms, 77, 1, None, _lib.ptr(grid_out), grid_out.stride(0),
+                                    _lib.stream_ptr(dev))
+        assert rc == 0, rc
+    res["calls"] = {"note": f"T = {T}, RBSize {RB} of {CARRIER_PRB}, Nr = {NR}, port 1000, DMRS symbols [2, 11], group "
+                            "hopping; ldpc5g_slot_rx_frontend_tp and ldpc5g_slot_map_tp (one antenna, identity), "
+                            "each call event-timed on its own, interleaved"}
+    for cdt, pname in ((torch.complex128, "complex128"), (torch.complex64, "complex64")):
+        rdt = torch.float64 if cdt == torch.complex128 else torch.float32
+        grid = torch.complex(torch.randn((T, NR, W), dtype=rdt, device=dev, generator=gen),
+                             torch.randn((T, NR, W), dtype=rdt, device=dev, generator=gen))
+        h_ls = torch.empty((T, S, 3 * RB, NR, 1), dtype=cdt, device=dev)
+        y = torch.empty((T, 14 * 12 * RB, NR), dtype=cdt, device=dev)
+
+        def raw_fe(h, yy):
+            rc = lib.ldpc5g_slot_rx_frontend_tp(
+                _lib.ptr(grid), grid.stride(0), _lib.F32 if cdt == torch.complex64 else _lib.F64, _lib.ptr(slots), T,
+                W // 14, 0, RB, NR, 0, S, syms, 77, 1, None, _lib.ptr(h) if h is not None else None, h_ls.stride(0),
+                _lib.ptr(yy) if yy is not None else None, y.stride(0), _lib.stream_ptr(dev))
+            assert rc == 0, rc
+        variants = {"pusch_tp_frontend/h_ls_only": lambda: raw_fe(h_ls, None),
+                    "pusch_tp_frontend/y_only": lambda: raw_fe(None, y),
+                    "pusch_tp_frontend/both": lambda: raw_fe(h_ls, y)}
+        if cdt == torch.complex64:
+            variants["pusch_tp_map"] = raw_map
+        for _ in range(1 if args.once else args.warmup):
+            for fn in variants.values():
+                fn()
+        if args.once:
+            for fn in variants.values():
+                fn()
+            torch.cuda.synchronize()
+            continue
+        times = {k: [] for k in variants}
+        for _ in range(args.steps):   # interleaved: every variant once per step
+            for k, fn in variants.items():
+                times[k].append(ev(fn))
+        res["calls"][pname] = {k: stats(v) for k, v in times.items()}
+        print(pname, "calls", json.dumps(res["calls"][pname]), flush=True)
+        del grid, h_ls, y
+    if args.once:
+        return
+
+    # ---- the chain: RBSize 270, 1 x 4, with and without transform precoding
     G = nre * Qm
     A = 19464
     scfg = sch.sch_config(A, Qm, 308, 1, 0, 0, G)
     tb = torch.randint(0, 2, (T, A), dtype=torch.int8, device=dev, generator=gen)
     cinit = torch.arange(T, device=dev, dtype=torch.int64) * 2 ** 15 + 7
     words = phy.prbs_words(cinit, G)
-    slots = (torch.arange(T, device=dev, dtype=torch.int32) % 20).contiguous()
     x = phy.scramble_modulate(sch.sch_encode_batch(tb, scfg).contiguous(), Qm, words=words)
     rng = np.random.default_rng(270)
     H = torch.tensor((rng.standard_normal((T, NR, 1)) + 1j * rng.standard_normal((T, NR, 1))) / np.sqrt(2)).to(dev)
