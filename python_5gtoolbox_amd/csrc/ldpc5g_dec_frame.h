@@ -243,6 +243,65 @@ constexpr int fr_cof(int i, int k) { return (fr_sft<BG>(i, k) - kFrPlan<BG>.off[
 template <int BG>
 constexpr int fr_pf(int i, int H) { return kFrPlan<BG>.kc[H][i] >= 0 ? fr_sft<BG>(i, kFrPlan<BG>.kc[H][i]) : 0; }
 
+// The final pass's syndrome, on bits.  The decisions are published as 384-bit vectors in LDS: one
+// per core column (entry order; 12 dwords and the first two again behind them, so that any
+// 64-bit window of the circular vector is three consecutive dwords) and one per extension row, in
+// the order of the row's frame (bit s: the decision thread s of the owner half holds), so a
+// wave's ballot is one aligned 64-bit word of it.  In that order the syndrome of row i, word w
+// (frame positions 64w .. 64w + 63), is the XOR over the row's core edges k of the window of
+// column j at bit (64w + fr_cof(i, k)) mod Zc, XOR word w of the row's extension vector.
+// Two lanes share a (row, word) pair and split its terms; tab[e][item] is the item's e-th term:
+// (LDS byte address of the window's first dword) << 5 | (its bit offset in that dword); unused
+// terms read a zero word.  The image lies in the wrap table and the hand-off spares, which
+// nothing reads after the loop.
+template <int BG>
+struct FrSyn {
+    static constexpr int KC = BGT<BG>::KC, MB = BGT<BG>::MB, NWD = kFrZ / 64;
+    static constexpr int CVB = 4 * (2 * NWD + 2), XVB = 4 * 2 * NWD;   // bytes per core / ext vector
+    static constexpr int NI = 2 * MB * NWD, NWV = (NI + 63) / 64;      // items (lanes), their waves
+    static constexpr int MAXT = 10;
+    int nxm = 0;                                   // extension vectors per half (xlist order)
+    int core_b = 0, ext_b = 0, zero_b = 0, end_b = 0;
+    int nt = 0, nt_rest = 0;                       // terms per item: wave 0 / the other waves
+    uint32_t tab[MAXT][NWV * 64] = {};
+    bool ok = true;
+    constexpr int xvec(int i) const { return ext_b + (kFrPlan<BG>.owner[i] * nxm + kFrPlan<BG>.xpos[i]) * XVB; }
+    constexpr FrSyn() {
+        using P = BGT<BG>;
+        nxm = kFrPlan<BG>.nx[0] > kFrPlan<BG>.nx[1] ? kFrPlan<BG>.nx[0] : kFrPlan<BG>.nx[1];
+        core_b = kFrPlan<BG>.tbl_b;
+        ext_b = core_b + KC * CVB;
+        zero_b = ext_b + 2 * nxm * XVB;
+        end_b = zero_b + 16;
+        ok = ok && core_b % 8 == 0 && end_b <= kFrPlan<BG>.bytes;
+        for (int e = 0; e < MAXT; ++e)
+            for (int x = 0; x < NWV * 64; ++x) tab[e][x] = (uint32_t)zero_b << 5;
+        for (int i = 0; i < MB; ++i) {
+            const int d = P::RS[i + 1] - P::RS[i], n0 = (d + 1) / 2;
+            ok = ok && d <= 2 * MAXT;
+            for (int w = 0; w < NWD; ++w)
+                for (int k = 0; k < d; ++k) {
+                    const int j = P::COL[P::RS[i] + k];
+                    const int item = 2 * (i * NWD + w) + (k >= n0), e = k >= n0 ? k - n0 : k;
+                    const int o = (64 * w + (fr_sft<BG>(i, k) - kFrPlan<BG>.off[i] + kFrZ)) % kFrZ;
+                    if (j < KC) {
+                        tab[e][item] = ((uint32_t)(core_b + j * CVB + (o >> 5) * 4) << 5) | (uint32_t)(o & 31);
+                    } else {
+                        ok = ok && i >= 4 && k == d - 1;
+                        tab[e][item] = (uint32_t)(xvec(i) + w * 8) << 5;
+                    }
+                    const int need = e + 1;
+                    if (item < 64) nt = nt > need ? nt : need;
+                    else nt_rest = nt_rest > need ? nt_rest : need;
+                }
+        }
+        nt = nt > nt_rest ? nt : nt_rest;
+    }
+};
+template <int BG>
+constexpr FrSyn<BG> kFrSyn{};
+static_assert(kFrSyn<1>.ok && kFrSyn<2>.ok, "bit image of the decisions inside the wrap table and the spares");
+
 // does half H add edge k of row i (a column >= 2) in phase B: LDS rows alternate edges between the
 // halves, a VGPR row's owner adds all of them
 template <int BG>
@@ -512,9 +571,13 @@ __device__ __forceinline__ void frame_body(
     // ---- iterations exhausted: ck = (LQ <= 0), status = syndrome == 0 (:133-143)
     int sv = s;
     asm volatile("" : "+v"(sv));   // keep the output addresses out of the loop
-    uint32_t sb = sb0, sbw = sbw0;
+    uint32_t sb = sb0;
     asm volatile("" : "+v"(sb));
-    asm volatile("" : "+v"(sbw));
+    using SY = FrSyn<BG>;
+    constexpr int NT = kFrSyn<BG>.nt;
+    const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    uint32_t se[NT];   // this lane's terms of the bit syndrome (FrSyn); no value before its loads:
+                       // a zero fill would keep NT registers live across the extension decisions
     auto xposf = [&](int i) -> int {
         const int c = (Z - kFrPlan<BG>.off[i]) % Z;
         if (c == 0) return sv;
@@ -545,34 +608,72 @@ __device__ __forceinline__ void frame_body(
                 });
             });
         });
-        bool fail = false;
+        // ---- the decisions as bit vectors (FrSyn): this item's terms first (their latency hides
+        // behind the rest); a wave's compare masks are 64-bit words of the vectors, gathered
+        // into lanes (lane jj: own column jj, lane KH + p: the half's extension row p, two
+        // lanes of zeros for the zero word) and stored with one write per wave
+        __builtin_amdgcn_sched_barrier(0);   // not above the extension decisions (registers)
+        if (wv < SY::NWV) {
+            // the lane-indexed copy of the table: a static local of the device function, so it
+            // exists in the code object alone (no host shadow variable, nothing to register)
+            static constexpr FrSyn<BG> kFrSynD{};
+            int tq = t;
+            asm volatile("" : "+v"(tq));   // keep the table's 64-bit lane offset out of the loop
+            sfor<0, NT>([&](auto ec) {
+                constexpr int e = decltype(ec)::value;
+                if (e < kFrSyn<BG>.nt_rest || wv == 0) se[e] = kFrSynD.tab[e][tq];
+            });
+        }
+        const int ln = t & 63;
+        uint32_t plo = 0, phi = 0;
+        sfor<0, KH>([&](auto jc) {
+            constexpr int jj = decltype(jc)::value;
+            const bool dn = at((uint32_t)(jcol(jj) * kFrColB) + sb) <= T(0);
+            oc |= (uint32_t)dn << jj;
+            const uint64_t m = __builtin_amdgcn_ballot_w64(dn);
+            plo = ln == jj ? (uint32_t)m : plo;
+            phi = ln == jj ? (uint32_t)(m >> 32) : phi;
+        });
         per_half([&](auto hc) {
             constexpr int hh = decltype(hc)::value;
-            constexpr uint64_t rows = [] {
-                uint64_t m = 0;
-                for (int i = 0; i < P::MB; ++i)
-                    if (kFrPlan<BG>.owner[i] == hh) m |= 1ull << i;
-                return m;
-            }();
-            fail = syndrome_fails<BG, rows, false, T>(
-                [&](auto ic, auto kc) -> T {
-                    constexpr int i = decltype(ic)::value, k = decltype(kc)::value;
-                    constexpr int c = (fr_sft<BG>(i, k) - kFrPlan<BG>.off[i] + Z) % Z;
-                    return at((uint32_t)(P::COL[P::RS[i] + k] * kFrColB) + fr_rot(sb, sbw, c));
-                },
-                [&](auto ic) -> bool { return (ox >> (decltype(ic)::value - 4)) & 1u; });
+            static_assert(KH + kFrPlan<BG>.nx[hh] + 2 <= 64, "one lane per published word");
+            sfor<0, kFrPlan<BG>.nx[hh]>([&](auto xc) {
+                constexpr int p = decltype(xc)::value, i = kFrPlan<BG>.xlist[hh][p];
+                const uint64_t m = __builtin_amdgcn_ballot_w64((ox >> (i - 4)) & 1u);
+                plo = ln == KH + p ? (uint32_t)m : plo;
+                phi = ln == KH + p ? (uint32_t)(m >> 32) : phi;
+            });
         });
-        if (fail) *flagA = 1;
-    }
+        const int ws = wv - h * (Z / 64), nxh = h ? kFrPlan<BG>.nx[1] : kFrPlan<BG>.nx[0];
+        const int lx = ln - KH;
+        uint32_t pa = (uint32_t)(kFrSyn<BG>.core_b + jcol(ln) * SY::CVB + ws * 8);
+        if (lx >= 0) pa = (uint32_t)(kFrSyn<BG>.ext_b + (h * kFrSyn<BG>.nxm + lx) * SY::XVB + ws * 8);
+        if (lx >= nxh) pa = (uint32_t)(kFrSyn<BG>.zero_b + (lx - nxh) * 8);
+        using lds_u64 = __attribute__((address_space(3))) uint64_t;
+        if (lx < nxh + 2) *(lds_u64*)(uintptr_t)pa = ((uint64_t)phi << 32) | plo;
+        if (ws == 0 && lx < 0) *(lds_u64*)(uintptr_t)(pa + (uint32_t)(SY::XVB)) = ((uint64_t)phi << 32) | plo;
+    } else {
 #pragma unroll
-    for (int jj = 0; jj < KH; ++jj) {
-        const T v = at((uint32_t)(jcol(jj) * kFrColB) + sb);
-        oc |= (uint32_t)(active ? v <= T(0) : v < T(0)) << jj;
+        for (int jj = 0; jj < KH; ++jj) oc |= (uint32_t)(at((uint32_t)(jcol(jj) * kFrColB) + sb) < T(0)) << jj;
     }
     lds_barrier();   // every LQ / state read is done: LDS below the flags is free from here
-    if (active && t == 0) {
-        status[out] = *flagA == 0;
-        iters[out] = L;
+    // ---- the syndrome of the published decisions, beside the ck staging below: each item XORs
+    // its windows, the two lanes of a (row, word) pair must agree
+    if (active && wv < SY::NWV) {
+        uint32_t xl = 0, xh = 0;
+        sfor<0, NT>([&](auto ec) {
+            constexpr int e = decltype(ec)::value;
+            if (e < kFrSyn<BG>.nt_rest || wv == 0) {
+                const uint32_t a = se[e] >> 5;
+                const uint32_t d0 = *(lds_u32*)(uintptr_t)a, d1 = *(lds_u32*)(uintptr_t)(a + 4u),
+                               d2 = *(lds_u32*)(uintptr_t)(a + 8u);
+                xl ^= __builtin_amdgcn_alignbit(d1, d0, se[e]);   // the shift is the low 5 bits
+                xh ^= __builtin_amdgcn_alignbit(d2, d1, se[e]);
+            }
+        });
+        xl ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xl, 0xB1, 0xf, 0xf, true);   // lane ^ 1
+        xh ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xh, 0xB1, 0xf, 0xf, true);
+        if ((xl | xh) != 0u) *flagA = 1;
     }
     // ---- ck through LDS (ck_store_staged, ldpc5g_dec_body.h)
     constexpr int NFZ = P::NB * Z;
@@ -586,7 +687,11 @@ __device__ __forceinline__ void frame_body(
                 ck_stage_byte((uint32_t)((KB + i) * Z + xposf(i)), (uint32_t)(ox >> (i - 4)) & 1u);
         });
     });
-    const bool slow = block_any(!ck_row_aligned(NFZ, crow));   // orders the staging too
+    const bool slow = block_any(!ck_row_aligned(NFZ, crow));   // orders the staging and the flag too
+    if (active && t == 0) {
+        status[out] = *flagA == 0;
+        iters[out] = L;
+    }
     ck_store_staged(NFZ, 1, [&](int) -> int8_t* { return crow; }, slow, t, kFrThreads);
 }
 

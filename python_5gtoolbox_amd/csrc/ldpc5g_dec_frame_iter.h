@@ -74,9 +74,14 @@
         // ---- phase A: new row state from LQ_old (:117-123, _min_sum_process :186-202).  The
         // half's core-edge stream (FrStream): entry p's wrap-table offset is read kFrDT positions
         // ahead and its LQ kFrDA ahead, across row boundaries (slots p % kFrDT, p % kFrDA)
+        // sg: the row's sign bits, old and new in one shift register.  It starts as the old
+        // signs left-aligned (get_state: edge 0 in bit 31) and moves left once per edge: that
+        // drops edge k's old sign (used for rold_k), brings edge k + 1's to bit 31 and takes
+        // edge k's new sign in at bit 0.  After the row's d edges its low d bits are the new
+        // signs, edge 0 in bit d - 1.
         struct RowSt {
             T mA, mB, min1, min2;
-            uint32_t u, idxo, idx, negs;
+            uint32_t sg, idxo, idx;
             bool par;
         };
         uint32_t tbs[kFrDT];
@@ -112,14 +117,14 @@
         };
         auto rowA = [&](auto ic) {
             constexpr int i = decltype(ic)::value, e0 = P::RS[i], d = kFrPlan<BG>.deg(i);
+            static_assert(d <= 19, "old and new signs of a row share one 32-bit register");
             RowSt r;
-            get_state(ic, r.mA, r.mB, r.u, r.idxo);
+            get_state(ic, r.mA, r.mB, r.sg, r.idxo);
             r.min1 = FT<T>::inf(), r.min2 = FT<T>::inf();
-            r.idx = 0, r.negs = 0, r.par = false;
+            r.idx = 0, r.par = false;
             sfor<0, d>([&](auto kc) {
                 constexpr int k = decltype(kc)::value, j = P::COL[e0 + k];
-                const T rold = xsign_v(pick(r.idxo == (uint32_t)k, r.mB, r.mA), r.u, mv);
-                asm("v_add_u32 %0, %1, %1" : "=v"(r.u) : "v"(r.u));   // u <<= 1, all-VGPR form
+                const T rold = xsign_v(pick(r.idxo == (uint32_t)k, r.mB, r.mA), r.sg, mv);
                 T a;
                 if constexpr (j < KC) {
                     a = snext(ic, kc);
@@ -136,7 +141,7 @@
                 const T aq = fabs(q);
                 r.idx = aq < r.min1 ? (uint32_t)k : r.idx;
                 asm volatile("" : "+v"(r.idx));
-                r.negs = __builtin_amdgcn_alignbit(r.negs, FT<T>::sbits(q), 31);
+                r.sg = __builtin_amdgcn_alignbit(r.sg, FT<T>::sbits(q), 31);
                 two_min(r.min1, r.min2, aq);
             });
             fail |= r.par;
@@ -145,8 +150,14 @@
                 x1 = r.min1 - beta, x2 = r.min2 - beta;   // max(minv - beta, 0) (:201)
                 x1 = x1 > T(0) ? x1 : T(0), x2 = x2 > T(0) ? x2 : T(0);
             }
-            const uint32_t sgn = 0u - (__builtin_popcount(r.negs) & 1u);   // the row's sign product
-            put_state(ic, alpha * x1, alpha * x2, r.negs ^ (sgn & ((1u << d) - 1u)), r.idx);
+            // above the d new signs sg holds zeros (get_state's word is p << (32 - d): nothing
+            // below the old signs), except in the high field of a shared word (ph == 2,
+            // p << (16 - d)): there the other row's field lay below and sits in bits 16.. now
+            constexpr uint32_t dm = (1u << d) - 1u;
+            uint32_t negs = r.sg;
+            if constexpr (!kFrPlan<BG>.lds[i] && kFrPlan<BG>.ph[i] == 2) negs &= dm;
+            const uint32_t sgn = 0u - (__builtin_popcount(negs) & 1u);   // the row's sign product
+            put_state(ic, alpha * x1, alpha * x2, (r.sg ^ sgn) & dm, r.idx);
         };
         // a dead extension row: LQ_ext = 0 + r_old_ext (its syndrome bit), q_core = LQ - (+-0); the
         // new state as the full update leaves it up to zero signs (ldpc5g_dec_flood.h rowA_dead)

@@ -324,8 +324,9 @@ _REDERIVE_FLAGS = [
 # instrumentation of the frame kernel (wrong ck rows): every workgroup records the real-time clock
 # (100 MHz) at 9 points — start, after the prologue's barrier, after the peeled iteration 0 (BG1:
 # the fused start, iteration 0 and iteration 1's phase A), after iterations 1 (BG1: its phase B
-# alone) and 2, loop exit, after the final pass's extension decisions, after its syndrome part
-# (and barrier), after the ck store — plus HW_ID and XCC_ID (which CU it ran on) into the first 88
+# alone) and 2, loop exit, after the final pass's extension decisions, after its core decisions,
+# the publishing of the decisions as bit vectors and the barrier (the bit syndrome runs behind that
+# stamp, beside the ck staging), after the ck store — plus HW_ID and XCC_ID (which CU it ran on) into the first 88
 # bytes of its ck row; frame_ts_fused adds two stamps inside the fused start, in the 16 bytes behind
 # (tools/frame_ts_probe.py reads them).  A 3-tuple patch names its own file.
 FRAME = "ldpc5g_dec_frame.h"
@@ -346,9 +347,10 @@ def _frame_ts(inner):
          "        if (FUSED ? !active : !block_any(active)) break;\n    }\n"),
         ("    int sv = s;\n    asm volatile(\"\" : \"+v\"(sv));   // keep the output addresses out of the loop\n",
          f"    ts[5] = {_RT};\n    int sv = s;\n    asm volatile(\"\" : \"+v\"(sv));   // keep the output addresses out of the loop\n"),
-        ("        bool fail = false;\n        per_half([&](auto hc) {\n            constexpr int hh = decltype(hc)::value;\n            constexpr uint64_t rows = [] {",
-         f"        ts[6] = {_RT};\n        bool fail = false;\n        per_half([&](auto hc) {{\n"
-         "            constexpr int hh = decltype(hc)::value;\n            constexpr uint64_t rows = [] {"),
+        # stamp 6 -> 7: the core decisions, the decisions published as bit vectors, the barrier; the
+        # bit syndrome itself runs behind stamp 7, beside the ck staging (stamp 7 -> 8)
+        ("        // ---- the decisions as bit vectors (FrSyn): this item's terms first",
+         f"        ts[6] = {_RT};\n        // ---- the decisions as bit vectors (FrSyn): this item's terms first"),
         ("    lds_barrier();   // every LQ / state read is done: LDS below the flags is free from here\n",
          f"    lds_barrier();   // every LQ / state read is done: LDS below the flags is free from here\n    ts[7] = {_RT};\n"),
         ("    ck_store_staged(NFZ, 1, [&](int) -> int8_t* { return crow; }, slow, t, kFrThreads);\n}\n",
