@@ -233,6 +233,32 @@ static_assert(kFrDA >= 1 && kFrDT > kFrDA, "stream read distances");
 #endif
 constexpr int kFrXPreFirst = LDPC5G_FR_XPRE_FIRST;
 static_assert(kFrXPreFirst >= 1, "ring depth");
+// The seam between two iterations (what is neither phase A nor a group block of phase B) is a run
+// of dependent LDS and L2 round trips with every wave of the CU in step.  Reorderings of it and of
+// phase A's issue order, each bit-neutral (the same loads, adds and stores in the same arithmetic
+// order).  The bits exist for A/B builds (tools/ab/make_variants.py frame_seam_*);
+// the product is 1 + 4 + 8 + 16:
+//   1  the loop's closing vote (block_any) is a plain barrier: `active` is workgroup-uniform
+//   2  (off: no gain alone, a loss beside the others) the next trip's cold-start loads (ext LLR
+//      ring, wrap-table offsets) go out before the last group barrier (plain kernels only)
+//   4  the LQ update's core LLRs go out before phase A's barrier, not after the flag test
+//   8  the LQ update reads all its own entries before the first add
+//  16  phase A's waves take issue priority by the share of their half's edge stream that they
+//      have left (fr_prio): the three waves of a SIMD otherwise leave phase A oldest first,
+//      microseconds apart, and the last runs alone at its own dependency-bound rate
+#ifndef LDPC5G_FR_SEAM
+#define LDPC5G_FR_SEAM 29
+#endif
+constexpr bool kSeamBar = (LDPC5G_FR_SEAM & 1) != 0, kSeamPre = (LDPC5G_FR_SEAM & 2) != 0,
+               kSeamLf = (LDPC5G_FR_SEAM & 4) != 0, kSeamUpd = (LDPC5G_FR_SEAM & 8) != 0,
+               kSeamPrio = (LDPC5G_FR_SEAM & 16) != 0;
+// s_setprio level of a wave about to run row i of its half: 3, 2, 1, 0 by the quarter of the
+// half's core-edge stream in which the row starts
+template <int BG>
+constexpr int fr_prio(int i) {
+    const int q = 4 * kFrStr<BG>.start[i] / kFrStr<BG>.n[kFrPlan<BG>.owner[i]];
+    return 3 - (q > 3 ? 3 : q);
+}
 
 // V(i, k) mod Zc of edge k of row i; the same relative to the row's frame (thread s runs check node
 // s - off, so edge k's column entry is s + fr_cof); frame of LDS row i for half H's phase B

@@ -42,6 +42,24 @@
     auto rdead = [&](int i) -> bool { return DEAD && i >= 4 && ((live_x >> (i - 4)) & 1u) == 0; };
     int* const flagI = FIRST ? flagA + 2 : flagA;
     constexpr bool FUSED = FIRST && BG == 1;   // the fused start, see the top
+    // ext LLR ring: slot p % XP holds the LLR of the half's ext row p, loaded XP rows ahead
+    // (FIRST: its own, deeper ring — those loads come from HBM, the loop's from L2)
+    constexpr int XP = FIRST ? kFrXPreFirst : kXPre > 0 ? kXPre : 1;
+    // The ring and the wrap-table offsets of the stream live across the loop's back edge: with PRE a
+    // trip issues the next trip's cold-start loads (the ring's first XP rows, the stream's first
+    // kFrDT table reads) before its last group barrier, and the next trip's phase A finds them
+    // there (`pre`: every trip but the loop's first).  Neither depends on anything the loop
+    // writes: the LLRs are the kernel's input and the wrap table is constant until the final pass.
+    // A workgroup that leaves the loop has loaded XP + kFrDT values for nothing.
+    constexpr bool PRE = kSeamPre && !FIRST && !KDEAD;
+    // the other steps of LDPC5G_FR_SEAM (ldpc5g_dec_frame.h), in the plain kernels only: the
+    // rate-matched (KDEAD) kernels run without them (their one --full line measured with steps
+    // 1, 4, 8 was slower, 2.087 against 2.011 ms per batch)
+    constexpr bool SBAR = kSeamBar && !KDEAD, SLF = kSeamLf && !KDEAD, SUPD = kSeamUpd && !KDEAD,
+                   SPRIO = kSeamPrio && !KDEAD;
+    T xr[XP];
+    uint32_t tbs[kFrDT];
+    bool pre = false;
     for (; it < (FIRST ? (L < 1 ? L : 1) : L); ++it) {
         // opaque per iteration: otherwise LICM hoists hundreds of loop-invariant addresses
         uint32_t sb = sb0, sbw = sbw0, tz = tz0;
@@ -63,10 +81,6 @@
         const bool runA = FIRST || !skipA;   // after the fused start: iteration 1's state is there,
         if (!runA) hdx = hdx_keep;           // and its decisions are those of the start's pass
 
-        // ext LLR ring: slot p % XP holds the LLR of the half's ext row p, loaded XP rows ahead
-        // (FIRST: its own, deeper ring — those loads come from HBM, the loop's from L2)
-        constexpr int XP = FIRST ? kFrXPreFirst : kXPre > 0 ? kXPre : 1;
-        T xr[XP];
         auto xload = [&](auto hc, auto pc_) {
             constexpr int hh = decltype(hc)::value, p = decltype(pc_)::value;
             if constexpr (p < kFrPlan<BG>.nx[hh]) xr[p % XP] = llrx(kFrPlan<BG>.xlist[hh][p]);
@@ -84,7 +98,6 @@
             uint32_t sg, idxo, idx;
             bool par;
         };
-        uint32_t tbs[kFrDT];
         T abq[kFrDA];
         auto sload_t = [&](auto hc, auto pc_) {
             constexpr int hh = decltype(hc)::value, p = decltype(pc_)::value;
@@ -329,15 +342,24 @@
             }
             put_first(ic, par, m1, m2, negs, idx);
         };
+        // phase A's cold start: the loads that need no LDS data of this trip
+        auto cold_start = [&](auto hc) {
+            sfor<0, XP>([&](auto pc_) { xload(hc, pc_); });
+            sfor<0, kFrDT>([&](auto pc_) { sload_t(hc, pc_); });
+        };
         if (active && runA) {
             per_half([&](auto hc) {
-                sfor<0, XP>([&](auto pc_) { xload(hc, pc_); });
-                sfor<0, kFrDT>([&](auto pc_) { sload_t(hc, pc_); });
-                sfor<0, kFrDA>([&](auto pc_) { sload_a(hc, pc_); });
+                if (!(PRE && pre)) cold_start(hc);   // else: issued by the trip before
+                sfor<0, kFrDA>([&](auto pc_) { sload_a(hc, pc_); });   // LQ: behind the barrier
             });
             sfor<0, MB>([&](auto ic) {   // one branch per row: bounded live ranges
                 constexpr int i = decltype(ic)::value;
                 if (h == kFrPlan<BG>.owner[i]) {
+                    if constexpr (SPRIO) {
+                        // a wave that is behind the others of its SIMD issues first (ldpc5g_dec_frame.h)
+                        constexpr int pr = fr_prio<BG>(i);
+                        __builtin_amdgcn_s_setprio(pr);
+                    }
                     if constexpr (FUSED) {
                         rowA_fused(ic);
                     } else if constexpr (FIRST) {
@@ -351,7 +373,23 @@
                     }
                 }
             });
+            if constexpr (SPRIO) __builtin_amdgcn_s_setprio(0);
             if (fail) *flagI = 1;
+        }
+        // the core LLRs of the LQ update.  SLF: issued before the barrier, so that they are
+        // on their way while the workgroup waits for it and for the flag's round trip (a
+        // codeblock that the syndrome test then decides has loaded them for nothing); else after
+        // the test.  Either way phase B hides the rest of their latency.
+        T lf[KH];
+        auto load_lf = [&]() {
+#pragma unroll
+            for (int jj = 0; jj < KH; ++jj) {
+                const int j = jcol(jj);
+                lf[jj] = ldg(lrow, (j < pc ? 0 : j - pc) * Z + sv);
+            }
+        };
+        if constexpr (SLF && !FUSED) {   // FUSED: the image of columns >= 2 holds LLR + (+0.0) already
+            if (active) load_lf();
         }
         lds_barrier();
         // ---- the syndrome of LQ_old decides (:107-114): output its hard decisions
@@ -375,14 +413,8 @@
             else __hip_atomic_fetch_add(&acc, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         };
         T S = T(0);
-        // the core LLRs of the LQ update, loaded now so phase B hides their latency
-        T lf[KH];
-        if (!FUSED && active) {   // FUSED: the image of columns >= 2 holds LLR + (+0.0) already
-#pragma unroll
-            for (int jj = 0; jj < KH; ++jj) {
-                const int j = jcol(jj);
-                lf[jj] = ldg(lrow, (j < pc ? 0 : j - pc) * Z + sv);
-            }
+        if constexpr (!SLF && !FUSED) {
+            if (active) load_lf();
         }
         if constexpr (FUSED) {
             // iteration 0's column sums: rows in order, a row with one punctured column H gives S
@@ -537,19 +569,50 @@
                     });
                 });
             }
+            if constexpr (PRE && g == kFrPlan<BG>.ng - 1) {
+                // the next trip's cold start, on its way through the last group barrier, the LQ
+                // update and the loop's closing barrier
+                if (active && it + 1 < L) per_half(cold_start);
+            }
             if (!gdead) lds_barrier();
         });
         // ---- LQ = LLRin + sum (:126) for the own entries
         if (!FIRST && active) {
+            if constexpr (SUPD) {
+                // every own entry read before the first add: one LDS round trip, not KH - 1
+                T xo[KH];
 #pragma unroll
-            for (int jj = 0; jj < KH; ++jj) {
-                const int j = jcol(jj);
-                lds_T& x = at((uint32_t)(j * kFrColB) + sb);
-                x = (j < pc ? T(0) : lf[jj]) + (jj == 0 ? S : x);   // punctured columns: LLR 0 (:43)
+                for (int jj = 0; jj < KH; ++jj) xo[jj] = jj == 0 ? S : at((uint32_t)(jcol(jj) * kFrColB) + sb);
+#pragma unroll
+                for (int jj = 0; jj < KH; ++jj) {
+                    const int j = jcol(jj);
+                    at((uint32_t)(j * kFrColB) + sb) = (j < pc ? T(0) : lf[jj]) + xo[jj];   // punctured columns: LLR 0 (:43)
+                }
+            } else {
+#pragma unroll
+                for (int jj = 0; jj < KH; ++jj) {
+                    const int j = jcol(jj);
+                    lds_T& x = at((uint32_t)(j * kFrColB) + sb);
+                    x = (j < pc ? T(0) : lf[jj]) + (jj == 0 ? S : x);   // punctured columns: LLR 0 (:43)
+                }
             }
         }
         if (!FIRST && t == 0) *flagA = 0;   // read before the phase-B barriers
         if constexpr (!FIRST) skipA = false;
-        // FUSED: the loop's first trip begins with the barrier (its phase A is done above)
-        if (FUSED ? !active : !block_any(active)) break;
+        pre = true;   // (PRE) a trip that follows finds its cold start issued above
+        if constexpr (FUSED) {
+            // the loop's first trip begins with the barrier (its phase A is done above)
+            if (!active) break;
+        } else if constexpr (SBAR) {
+            // `active` is workgroup-uniform here: every thread starts with it set and clears it
+            // on the same test of the same LDS word (*flagI, read after phase A's barrier and
+            // not written again before the next barrier: flagA's reset above comes after at
+            // least one phase-B barrier, the peeled iteration's flag word is never reset).  So a
+            // vote through LDS (block_any) would decide nothing: a plain barrier orders the LQ
+            // update and the flag reset before the next trip, and every thread leaves alike.
+            lds_barrier();
+            if (!active) break;
+        } else {
+            if (!block_any(active)) break;
+        }
     }

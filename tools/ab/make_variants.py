@@ -342,9 +342,9 @@ def _frame_ts(inner):
         ("    lds_barrier();\n    uint64_t live_x = ~0ull;\n", f"    lds_barrier();\n    ts[1] = {_RT};\n    uint64_t live_x = ~0ull;\n"),
         ("    if (!active) {   // decided by the raw LLRs' syndrome\n",
          f"    ts[2] = {_RT};\n    if (!active) {{   // decided by the raw LLRs' syndrome\n"),
-        (FRAME_ITER, "        if (FUSED ? !active : !block_any(active)) break;\n    }\n",
+        (FRAME_ITER, "        pre = true;   // (PRE) a trip that follows finds its cold start issued above\n",
          f"        if (!FIRST && it == 1) ts[3] = {_RT};\n        if (!FIRST && it == 2) ts[4] = {_RT};\n"
-         "        if (FUSED ? !active : !block_any(active)) break;\n    }\n"),
+         "        pre = true;   // (PRE) a trip that follows finds its cold start issued above\n"),
         ("    int sv = s;\n    asm volatile(\"\" : \"+v\"(sv));   // keep the output addresses out of the loop\n",
          f"    ts[5] = {_RT};\n    int sv = s;\n    asm volatile(\"\" : \"+v\"(sv));   // keep the output addresses out of the loop\n"),
         # stamp 6 -> 7: the core decisions, the decisions published as bit vectors, the barrier; the
@@ -377,6 +377,51 @@ def _frame_ts(inner):
 # frame_ts_fused: also the two stamps inside the fused start (their four SGPRs cost the plain BG1
 # kernel 44 B/lane of scratch, which slows its steady iterations: read only the start's split there)
 VARIANTS.update({"frame_ts": (FRAME, _frame_ts(False)), "frame_ts_fused": (FRAME, _frame_ts(True))})
+
+
+# the seam between two iterations of the frame kernel: lane 0 of every wave writes
+# the real-time clock (100 MHz) at 8 points of iterations 4 and 5 — 0: phase A's cold-start LDS
+# reads are back (the s_waitcnt in front of the clock read waits for them), 1: after phase A's last
+# row, 2: after the barrier and the flag test, 3: after group 0's barrier, 4: after the last group's
+# barrier, 5: after the LQ update, 6: after the loop's closing barrier (the top of iteration 5),
+# 7: as 0, in iteration 5 — straight into the first 768 bytes of the workgroup's ck row, [wave][8].
+# Nothing is held in registers (frame_ts_fused's extra SGPRs spilled); the final ck store is left
+# out instead (wrong ck rows).  tools/frame_seam_probe.py reads them.  The anchors are lines that
+# the seam reorderings leave alone, so the same patches measure any LDPC5G_FR_SEAM setting.
+_SEAM_TS = [
+    ("    const T* lrow_x = lrow + (KB - pc) * Z;",
+     "    auto seam_stamp = [&](int k) {\n"
+     f"        if ((t & 63) == 0) ((uint64_t*)crow)[(t >> 6) * 8 + k] = {_RT};\n    }};\n"
+     "    const T* lrow_x = lrow + (KB - pc) * Z;"),
+    ("    ck_store_staged(NFZ, 1, [&](int) -> int8_t* { return crow; }, slow, t, kFrThreads);\n}\n", "}\n"),
+    (FRAME_ITER, "        bool fail = false;\n        uint64_t hdx = 0;",
+     "        if (!FIRST && it == 5) seam_stamp(6);\n        bool fail = false;\n        uint64_t hdx = 0;"),
+    (FRAME_ITER, "            sfor<0, MB>([&](auto ic) {   // one branch per row: bounded live ranges\n",
+     "            if (!FIRST && (it == 4 || it == 5)) seam_stamp(it == 4 ? 0 : 7);\n"
+     "            sfor<0, MB>([&](auto ic) {   // one branch per row: bounded live ranges\n"),
+    (FRAME_ITER, "            if (fail) *flagI = 1;\n        }\n",
+     "            if (fail) *flagI = 1;\n        }\n        if (!FIRST && it == 4) seam_stamp(1);\n"),
+    (FRAME_ITER, "            active = false;\n        }\n",
+     "            active = false;\n        }\n        if (!FIRST && it == 4) seam_stamp(2);\n"),
+    (FRAME_ITER, "            if (!gdead) lds_barrier();\n        });\n",
+     "            if (!gdead) lds_barrier();\n"
+     "            if constexpr (g == 0) {\n                if (it == 4) seam_stamp(3);\n            }\n        });\n"
+     "        if (!FIRST && it == 4) seam_stamp(4);\n"),
+    (FRAME_ITER, "        if (!FIRST && t == 0) *flagA = 0;   // read before the phase-B barriers\n",
+     "        if (!FIRST && it == 4) seam_stamp(5);\n"
+     "        if (!FIRST && t == 0) *flagA = 0;   // read before the phase-B barriers\n"),
+]
+
+
+def _seam(mask):
+    return ("#define LDPC5G_FR_SEAM 29\n", f"#define LDPC5G_FR_SEAM {mask}\n")
+
+
+# frame_seam_<mask>: the steps of LDPC5G_FR_SEAM (ldpc5g_dec_frame.h) alone and together (mask 0: none
+# of them, 29: the product); frame_seam_ts: the stamps on the product; frame_seam_ts0: on the kernel
+# without the steps
+VARIANTS.update({f"frame_seam_{m}": (FRAME, [_seam(m)]) for m in (0, 1, 2, 4, 8, 16, 5, 13, 15, 21, 31)})
+VARIANTS.update({"frame_seam_ts": (FRAME, _SEAM_TS), "frame_seam_ts0": (FRAME, _SEAM_TS + [_seam(0)])})
 
 
 def make(name):
