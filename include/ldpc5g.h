@@ -791,6 +791,78 @@ int ldpc5g_polar_decode(const void* plan_dev, const void* plan_host, const doubl
                         int64_t ldc, uint8_t* status, double* pm, int32_t B, int32_t algo, int32_t L,
                         void* stream);
 
+/* ================================================ UCI on PUSCH (TS 38.212 §5.3.3, §6.2.7, §6.3.2.4)
+ * The reference's py5gphy/smallblock, nr_ulsch_info.py and nr_pusch_datactrl_multiplex.py, batched over
+ * T rows (slots / transport blocks), bits int8, LLRs float32 or float64 (LDPC5G_F32 / LDPC5G_F64).
+ *
+ * ldpc5g_uci_rm_info is host-only: getULSCH_RM_info (nr_ulsch_info.py:6-170) with O = Enable * NumBits
+ * for each of HARQ-ACK, CSI part 1 and CSI part 2.  out[9] = Euci_ack, Qbar_ACK, Euci_CSI1, Qbar_CSI1,
+ * Euci_CSI2, Qbar_CSI2, Euci_ackrvd, Qbar_ACKrvd, G_ULSCH.  The ceilings are taken of the reference's
+ * double products in its order.  Where the reference asserts (an E above 8192 or below the payload's
+ * minimum capacity, Gtotal < Euci_CSI1 + Euci_CSI2, an offset index outside its table) or divides by
+ * ULSCH_size = 0, LDPC5G_ESIZE and a message.  Both host functions check the allocation the same way: RBSize
+ * 1..275, the symbols inside the slot, 1..14 DMRS symbols each in 0..13, NL 1..4, Qm in {1, 2, 4, 6, 8}.
+ *
+ * ldpc5g_uci_map_plan is host-only and linear in Gtotal (flags per resource element): the §6.2.7 map
+ * of nr_pusch_datactrl_multiplex.py:7-267 for one configuration, no frequency hopping (refused),
+ * NumCDMGroupsWithoutData 1 or 2, no UCI on DMRS symbols.  It returns the plan's size in bytes (plan ==
+ * NULL: size only) or a negative error (LDPC5G_ESIZE also where the reference would index past a list:
+ * UCI that does not fit, stream lengths that are not the allocation's).  The caller keeps the host copy
+ * and uploads one device copy; the entry points take both and check the host copy's header.  Layout:
+ *   int32 header[32]: magic "UCIP", version, bytes, Gtotal, Qm, NL, OACK, OCSI1, OCSI2, EnableULSCH,
+ *                     len[4] (UL-SCH, ACK, CSI1, CSI2 stream lengths; 0 for an absent stream),
+ *                     byte offset of fwd, byte offset of inv, punctured bits, ninv = sum of len,
+ *                     x placeholders, y placeholders; the rest 0
+ *   uint32 fwd[Gtotal]: for position t of g_seq, the stream that finally owns it and the index in it
+ *   uint32 inv[ninv]:   for each stream element (the four streams one after another), its position t
+ *   entry bits: 0..23 index or t; 24..26 stream (0 UL-SCH, 1 ACK, 2 CSI1, 3 CSI2, 4 none: left 0);
+ *               27..28 kind of a 1-2 bit HARQ-ACK position (0 data, 1 placeholder x, 2 placeholder y);
+ *               29 punctured: in fwd, a 1-2 bit HARQ-ACK position that overwrites another stream (step 5
+ *               on the reserved set); in inv, the overwritten element of that stream (UL-SCH, or CSI
+ *               part 2 placed on reserved resource elements), which still points at the position.
+ *
+ * Kernels, asynchronous on `stream`, no allocation, one launch each.  Limits, checked on the host
+ * BEFORE any HIP call: a plan with the right magic, version and sizes; T in 1..65535 (small-block
+ * decode: 1..2^22); every row stride at least its row; non-null buffers for every stream the plan holds.
+ *   uci_mux       g_seq[t] = stream[index] (data_control_multiplex; a position without a stream is 0)
+ *   uci_demux     the four streams of llr [T][ldl] (Gtotal used).  prbs == NULL: the permutation of
+ *                 data_control_separate, punctured LLRs left inside g_ulsch as the reference leaves
+ *                 them.  prbs != NULL (packed words of ldpc5g_prbs, the input still scrambled):
+ *                 ordinary positions times 1 - 2 c[t], a y position times 1 - 2 c[t - 1], an x position
+ *                 +0.  erase_punctured = 1 writes +0 for elements marked punctured.
+ *   uci_scramble_modulate   38.211 §6.3.1.1 with placeholders (x = -1 -> 1, y = -2 -> the scrambled
+ *                 bit before it, everything else XOR c) and the mapper of ldpc5g_scramble_modulate;
+ *                 mod in {1, -1, 2, 4, 6, 8}; prbs is required.  A y may stand anywhere: one that opens a symbol, or
+ *                 follows other y, repeats the nearest scrambled bit before the run (0 if the run starts the row),
+ *                 as the reference's sequential loop does.  Values other than 0, 1, -1, -2 are not checked.
+ *   smallblock_encode   bits [T][ldb] (K in 1..11 used) -> out [T][ldo] (E in 1..8192): §5.3.3 repeated
+ *                 to E (encode_uci_on_ulsch); K = 1, 2 use Qm and produce the placeholders -1 / -2.
+ *   smallblock_decode   llr [T][ldl] (E used) -> K bits: the E LLRs folded modulo N (Qm, 3 Qm or 32) by
+ *                 summing the repetitions in ascending order in float64, then the maximum-likelihood
+ *                 message, ties to the smallest message read MSB first; placeholders x are ignored,
+ *                 K = 1 with Qm >= 2 adds the y position. */
+int ldpc5g_uci_rm_info(int32_t RBSize, int32_t StartSymbolIndex, int32_t NrOfSymbols, const int32_t* dmrs_symlist,
+                       int32_t num_dmrs, int32_t NL, int32_t Qm, double coderateby1024, int64_t ULSCH_size,
+                       int32_t EnableULSCH, int32_t OACK, int32_t OCSI1, int32_t OCSI2, int32_t I_HARQ_ACK_offset,
+                       int32_t I_CSI1offset, int32_t I_CSI2offset, double UCIScaling, int64_t Gtotal, int64_t* out);
+int64_t ldpc5g_uci_map_plan(int32_t RBSize, int32_t StartSymbolIndex, int32_t NrOfSymbols, const int32_t* dmrs_symlist,
+                            int32_t num_dmrs, int32_t NumCDMGroupsWithoutData, int32_t NL, int32_t Qm, int32_t OACK,
+                            int32_t OCSI1, int32_t OCSI2, int32_t EnableULSCH, int32_t frequency_hopping, int64_t Euci_ack,
+                            int64_t Euci_CSI1, int64_t Euci_CSI2, int64_t Euci_ackrvd, int64_t G_ULSCH, int64_t Gtotal,
+                            void* plan, int64_t plan_bytes);
+int ldpc5g_uci_mux(const void* plan_dev, const void* plan_host, const int8_t* g_ulsch, int64_t ld_ulsch, const int8_t* g_ack,
+                   int64_t ld_ack, const int8_t* g_csi1, int64_t ld_csi1, const int8_t* g_csi2, int64_t ld_csi2, int8_t* g_seq,
+                   int64_t ldg, int32_t T, void* stream);
+int ldpc5g_uci_demux(const void* plan_dev, const void* plan_host, const void* llr, int32_t dtype, int64_t ldl,
+                     const uint32_t* prbs, int64_t ldw, int32_t erase_punctured, void* g_ulsch, int64_t ld_ulsch, void* g_ack,
+                     int64_t ld_ack, void* g_csi1, int64_t ld_csi1, void* g_csi2, int64_t ld_csi2, int32_t T, void* stream);
+int ldpc5g_uci_scramble_modulate(const int8_t* bits, int64_t ldb, const uint32_t* prbs, int64_t ldw, int32_t T, int64_t nbits,
+                                 int32_t mod, void* sym, int64_t ldsym, void* stream);
+int ldpc5g_smallblock_encode(const int8_t* bits, int64_t ldb, int32_t K, int32_t Qm, int8_t* out, int64_t ldo, int32_t E,
+                             int32_t T, void* stream);
+int ldpc5g_smallblock_decode(const void* llr, int32_t dtype, int64_t ldl, int32_t E, int32_t K, int32_t Qm, int8_t* out,
+                             int64_t ldo, int32_t T, void* stream);
+
 /* ================================================ gather records (multi-GPU)
  * Record r (a row of rec, stride ldr bytes) = the nbits int8 bits of row r of `bits` (values 0/1)
  * packed in np.packbits order (bit i -> byte i/8, bit 7 - i%8, tail zero-padded), then

@@ -189,6 +189,23 @@ SIGNATURES = {
                                              _c.c_void_p]),
     "ldpc5g_polar_decode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
                                        _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p]),
+    "ldpc5g_uci_rm_info": (_c.c_int, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
+                                      _c.c_double, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
+                                      _c.c_int32, _c.c_int32, _c.c_double, _c.c_int64, _c.c_void_p]),
+    "ldpc5g_uci_map_plan": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
+                                         _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int64,
+                                         _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64]),
+    "ldpc5g_uci_mux": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                  _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p]),
+    "ldpc5g_uci_demux": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p, _c.c_int64,
+                                    _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
+                                    _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p]),
+    "ldpc5g_uci_scramble_modulate": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
+                                                _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "ldpc5g_smallblock_encode": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_int64,
+                                            _c.c_int32, _c.c_int32, _c.c_void_p]),
+    "ldpc5g_smallblock_decode": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32,
+                                            _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p]),
     "ldpc5g_pack_records": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                        _c.c_void_p]),

@@ -14,6 +14,7 @@
 
 #include "ldpc5g_common.h"
 #include "ldpc5g_demod.h"
+#include "ldpc5g_mod.h"
 #include "ldpc5g_prbs.h"
 
 namespace ldpc5g_impl {
@@ -79,8 +80,7 @@ __global__ __launch_bounds__(256) void prbs_kernel(const uint32_t* __restrict__ 
 // scrambled bit b'(i) = b(i) + c(i) mod 2; symbol = (level_re + j level_im) / sqrt(scale) in the
 // reference's float32 arithmetic: levels exact, then numpy's complex64 division by a real scalar,
 // i.e. a multiply by the float32 reciprocal scl = 1 / float32(sqrt(scale)).
-// QM = 1: BPSK (re = im = 1 - 2b, nrModulation.py:15-16); with PI2, odd symbols re = 2b - 1
-// (pi/2-BPSK, :17-21).  QM = 10: 1024QAM (:38-42).
+// (the levels: mod_symbol, ldpc5g_mod.h, shared with ldpc5g_uci.hip)
 template <int QM, bool PI2>
 __global__ __launch_bounds__(256) void scramble_modulate_kernel(const int8_t* __restrict__ bits,
                                                                 int64_t ldb,
@@ -96,24 +96,7 @@ __global__ __launch_bounds__(256) void scramble_modulate_kernel(const int8_t* __
     float u[QM];
 #pragma unroll
     for (int i = 0; i < QM; ++i) u[i] = 1.0f - 2.0f * (float)(((uint32_t)b[i] ^ (c >> i)) & 1u);
-    float re, im;
-    if constexpr (QM == 1) {
-        re = (PI2 && (m & 1)) ? -u[0] : u[0], im = u[0];
-    } else if constexpr (QM == 2) {
-        re = u[0], im = u[1];
-    } else if constexpr (QM == 4) {
-        re = u[0] * (2.0f - u[2]), im = u[1] * (2.0f - u[3]);
-    } else if constexpr (QM == 6) {
-        re = u[0] * (4.0f - u[2] * (2.0f - u[4]));
-        im = u[1] * (4.0f - u[3] * (2.0f - u[5]));
-    } else if constexpr (QM == 8) {
-        re = u[0] * (8.0f - u[2] * (4.0f - u[4] * (2.0f - u[6])));
-        im = u[1] * (8.0f - u[3] * (4.0f - u[5] * (2.0f - u[7])));
-    } else {
-        re = u[0] * (16.0f - u[2] * (8.0f - u[4] * (4.0f - u[6] * (2.0f - u[8]))));
-        im = u[1] * (16.0f - u[3] * (8.0f - u[5] * (4.0f - u[7] * (2.0f - u[9]))));
-    }
-    sym[(int64_t)t * ldsym + m] = make_float2(re * scl, im * scl);
+    sym[(int64_t)t * ldsym + m] = mod_symbol<QM, PI2>(u, m, scl);
 }
 
 // ===================================================================== soft demodulation

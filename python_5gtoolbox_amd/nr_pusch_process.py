@@ -5,7 +5,8 @@ precoding of one slot's g_seq.
     nr_pusch_process(g_seq, rnti, nID, Qm, num_of_layers, nTransPrecode, RBSize, nNrOfAntennaPorts,
                      precoding_matrix) -> (nNrOfAntennaPorts, G / Qm / num_of_layers) complex64
 
-A g_seq holding the UCI placeholders -1 / -2 is refused (UCI on PUSCH is not provided).
+A g_seq holding the UCI placeholders -1 / -2 is refused here (UCI on PUSCH is not provided by this
+drop-in): uci.scramble_modulate is the batched entry point that applies the placeholder rules.
 """
 import numpy as np
 
@@ -17,7 +18,8 @@ def nr_pusch_process(g_seq, rnti, nID, Qm, num_of_layers, nTransPrecode, RBSize,
     g = np.asarray(g_seq)
     assert g.ndim == 1
     if (g < 0).any():
-        raise NotImplementedError("g_seq holds UCI placeholder bits (-1 / -2): UCI on PUSCH is not provided")
+        raise NotImplementedError("g_seq holds UCI placeholder bits (-1 / -2): UCI on PUSCH is not provided by this "
+                                  "drop-in; uci.scramble_modulate scrambles and maps a g_seq with placeholders")
     assert Qm in [1, 2, 4, 6, 8]
     assert nTransPrecode in [0, 1]
     NL = int(num_of_layers)

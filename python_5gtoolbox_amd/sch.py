@@ -13,6 +13,8 @@ one configuration — the C-ABI entry points ldpc5g_sch_* of include/ldpc5g.h.
         maximum-likelihood detector: phy.ml_detect, whose LLRs go straight to sch_decode_batch)
     sch_ce_eq_rx_batch / sch_ce_ml_rx_batch(y, h_ls, ce, algo, re_idx, mod, cfg, L, ...)   (the same
         from the DMRS least-squares estimate: phy.channel_estimate first)
+    sch_uci_tx_batch(trblk, uci_bits, uci_plan, cfg, mod, cinit) -> sym[T, Gtotal/Qm]   (UCI on PUSCH:
+    sch_uci_rx_batch(sym, noise_var, mod, uci_plan, cfg, L, cinit) -> (SchDecodeResult, dict)   uci.py)
 
 Device tensors in, device tensors out, everything asynchronous on the current stream; torch only
 allocates the buffers.  The per-transport-block drop-ins (nr_dlsch.DLSCHEncode,
@@ -353,6 +355,61 @@ def sch_rx_batch(sym, noise_var, mod, cfg, L, algo="min-sum", alpha=1.0, beta=0.
         sch_tb_check_batch(ws.dec_ck, cfg, T, ws)
     return SchDecodeResult(ws.tb_ok, ws.tbblk, llr_dn, ws.dec_ck, ws.status, ws.iters, ws.cb_ok,
                            ws.tb_rem)
+
+
+# ------------------------------------------------------------ UCI on PUSCH
+def sch_uci_tx_batch(trblk, uci_bits, uci_plan, cfg, mod, cinit=None, words=None, ws=None):
+    """The transmit chain of T PUSCH slots that carry UCI (ULSCHandUCIProcess, nr_pusch_uci.py:52-107,
+    then nr_pusch_process.py:14-30): trblk (T, >= A) int8 (None when the plan holds no UL-SCH), uci_bits a
+    dict with the payloads "ack" / "csi1" / "csi2" as (T, O) int8 for every stream the plan holds, cfg the
+    UL-SCH's sch_config with G = G_ULSCH -> symbols (T, Gtotal / Qm) complex64, scrambled by cinit (T,) or
+    precomputed phy.prbs_words of Gtotal bits."""
+    from . import phy, uci
+    t = _lib.require_gpu()
+    p = uci_plan
+    assert phy.bits_per_symbol(mod) == p.Qm, "modulation does not match the plan's Qm"
+    assert cinit is not None or words is not None, "cinit or words: the placeholders are defined by the scrambler"
+    g = {n: None for n in uci.STREAMS}
+    if p.lens["ulsch"]:
+        assert cfg.E_total == p.lens["ulsch"] and cfg.Qm == p.Qm, "cfg must be the UL-SCH's configuration with G = G_ULSCH"
+        g["ulsch"] = sch_encode_batch(trblk, cfg, ws)
+    for n, A in (("ack", p.OACK), ("csi1", p.OCSI1), ("csi2", p.OCSI2)):
+        if A:
+            b = uci_bits[n]
+            assert b.dim() == 2 and b.dtype == t.int8 and b.shape[1] == A, f"uci_bits[{n!r}]: (T, {A}) int8"
+            g[n] = uci.encode(b, p.lens[n], p.Qm)
+    return uci.scramble_modulate(uci.mux(p, g["ulsch"], g["ack"], g["csi1"], g["csi2"]), mod, cinit, words)
+
+
+def sch_uci_rx_batch(sym, noise_var, mod, uci_plan, cfg, L, cinit=None, words=None, algo="min-sum", alpha=1.0, beta=0.0,
+                     schedule="flooding", harq_in=None, dn_dtype=None, ws=None, uci_L=8, erase_punctured=True):
+    """The receive chain of T PUSCH slots that carry UCI, from equalised symbols (T, >= Gtotal / Qm) and
+    their noise variances: phy.demod_descramble without descrambling, uci.demux in descrambling mode
+    (placeholders by their rule, punctured UL-SCH LLRs erased unless erase_punctured=False),
+    sch_decode_batch on the UL-SCH stream (cfg: its sch_config with G = G_ULSCH; skipped when the plan
+    holds no UL-SCH) and uci.decode on every UCI stream with list size uci_L.
+    Returns (SchDecodeResult or None, dict): the dict holds "ack" / "csi1" / "csi2" -> (T, O) int8 bits and
+    "<name>_crc_ok" -> (T,) bool for payloads of 12 bits and more (None below), for the streams present."""
+    from . import phy, uci
+    t = _lib.require_gpu()
+    p = uci_plan
+    assert phy.bits_per_symbol(mod) == p.Qm, "modulation does not match the plan's Qm"
+    assert cinit is not None or words is not None, "cinit or words: the placeholders are defined by the scrambler"
+    nsym = p.Gtotal // p.Qm
+    assert sym.dim() == 2 and sym.shape[1] >= nsym and noise_var.shape[1] >= nsym
+    f64 = int(mod) == 1 and sym.dtype == t.complex128   # demod_bpsk.py:9 keeps float64
+    llr = phy.demod_descramble(sym[:, :nsym], noise_var[:, :nsym], mod, llr_dtype=t.float64 if f64 else None)
+    s = uci.demux(p, llr, cinit, words, erase_punctured)
+    res = None
+    if p.lens["ulsch"]:
+        assert cfg.E_total == p.lens["ulsch"] and cfg.Qm == p.Qm, "cfg must be the UL-SCH's configuration with G = G_ULSCH"
+        dn_dtype = dn_dtype or (t.float32 if schedule == "layered" else t.float64)
+        res = sch_decode_batch(s.ulsch, cfg, L, algo, alpha, beta, schedule, harq_in, dn_dtype, ws)
+    out = {}
+    for n, A in (("ack", p.OACK), ("csi1", p.OCSI1), ("csi2", p.OCSI2)):
+        if A:
+            out[n], out[n + "_crc_ok"] = uci.decode(getattr(s, n), A, p.lens[n], p.Qm, uci_L)
+    return res, out
 
 
 def sch_eq_rx_batch(y, h, cov, algo, re_idx, mod, cfg, L, re_per_cov=12, **kw):
