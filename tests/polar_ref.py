@@ -356,3 +356,146 @@ def cbsegment(bits, Euci):
     else:
         C, L, parts = 1, (6 if A <= 19 else 11), bits.reshape(1, -1)
     return np.stack([crc_attach(p, L) for p in parts]), C, Euci // C
+
+
+# ------------------------------------------------------------------ shapes of the parity sweeps
+# One list for the recorded fixture's generator, the GPU sweep and the CPU plan test, drawn with a
+# generator of its own so that it is the same under every numpy.
+SWEEP_L = (1, 2, 3, 4, 5, 7, 8, 12, 16)
+SWEEP_FIELDS = ("K", "E", "nMax", "iIL", "CRCLEN", "padCRC", "rnti", "iBIL", "algo", "L")
+_FAMS = ("dl", "dlpad", "ulpc", "ul11")   # BCH-like, DCI-like (24 ones, rnti), UCI with PC bits, UCI CRC11
+
+
+class _Lcg:
+    def __init__(self, seed):
+        self.s = seed & (2 ** 64 - 1)
+
+    def below(self, n):
+        self.s = (self.s * 6364136223846793005 + 1442695040888963407) % 2 ** 64
+        return (self.s >> 33) % n
+
+    def between(self, a, b):
+        return a + self.below(b - a + 1)
+
+
+def branch(K, E, N):
+    """The rate-matching mode, puncturing split by its ulim branch."""
+    m = mode(K, E, N)
+    return m if m != "punct" else ("punct_hi" if 4 * E >= 3 * N else "punct_lo")
+
+
+def sweep_shapes(seed, per_N, Emax, L1024, forced=(), Kdl=164):
+    """per_N shapes (dicts of SWEEP_FIELDS) for every N in 32..1024, cycling through the rate-matching
+    branches and code families that N admits, plus `forced` (K, E, nMax) triples.  Kdl: the largest K with
+    nMax = 9."""
+    g = _Lcg(seed)
+    out = []
+    for n in range(5, 11):
+        N = 1 << n
+        cells = {}
+        for _ in range(6000):
+            fam = _FAMS[g.below(4)]
+            nMax = 9 if fam in ("dl", "dlpad") else 10
+            K = g.between(25, Kdl) if nMax == 9 else (g.between(18, 25) if fam == "ulpc" else
+                                                    g.between(31, min(1023, N)) if g.below(2) else g.between(31, 1023))
+            lo = K + (3 if fam == "ulpc" else 0)
+            hi = (9 * N) // 8 if g.below(2) else Emax
+            if hi < lo:
+                continue
+            E = g.between(lo, hi)
+            if n_value(K, E, nMax) != n or K > N:
+                continue
+            cells.setdefault((branch(K, E, N), fam), []).append((K, E, nMax))
+        brs = sorted({c[0] for c in cells})
+        for i in range(per_N):
+            br = brs[i % len(brs)]
+            fams = [f for f in _FAMS if (br, f) in cells]
+            fam = fams[(i // len(brs) + i) % len(fams)]
+            lst = cells[(br, fam)]
+            out.append(_shape(g, *lst[g.below(len(lst))], len(out), L1024))
+    for K, E, nMax in forced:
+        out.append(_shape(g, K, E, nMax, len(out), L1024))
+    return out
+
+
+def _shape(g, K, E, nMax, i, L1024):
+    N = 1 << n_value(K, E, nMax)
+    iIL, crclen = (1, 24) if nMax == 9 else (0, 6 if K <= 25 else 11)
+    pad = int(iIL and g.below(2))
+    rnti = g.between(1, 0xffff) if pad else (g.between(1, (1 << crclen) - 1) if not iIL and g.below(2) else 0)
+    iBIL = 0 if 25 < K <= 30 or K == 18 else g.below(2)   # the reference refuses iBIL = 1 for these K
+    Ls = [L for L in SWEEP_L if N < 1024 or L <= L1024]
+    algo, L = ("SC", 1) if i % 6 == 5 else ("SCL", Ls[(i + i // len(Ls)) % len(Ls)])
+    return dict(K=K, E=E, nMax=nMax, iIL=iIL, CRCLEN=crclen, padCRC=pad, rnti=rnti, iBIL=iBIL, algo=algo, L=L)
+
+
+def plan_args(s):
+    return (s["K"], s["E"], s["nMax"], s["iIL"], s["CRCLEN"], s["padCRC"], s["rnti"])
+
+
+def sweep_coverage(shapes):
+    """What a shape list must cover; asserted wherever a list is used."""
+    byN = {}
+    for s in shapes:
+        byN.setdefault(1 << n_value(s["K"], s["E"], s["nMax"]), []).append(s)
+    assert sorted(byN) == [32, 64, 128, 256, 512, 1024] and all(len(v) >= 8 for v in byN.values())
+    for N, lst in byN.items():
+        have = {branch(s["K"], s["E"], N) for s in lst}
+        want = {"rep", "short"} | ({"punct_hi", "punct_lo"} if N >= 64 else set())   # N = 32 admits no puncturing
+        assert want <= have, (N, want - have)
+        assert {s["iBIL"] for s in lst} == {0, 1} and {s["algo"] for s in lst} == {"SC", "SCL"}, N
+    pcs = {construct(s["K"], s["E"], s["nMax"])[3:] for s in shapes}
+    assert {(3, 0), (3, 1), (0, 0)} <= pcs
+    assert {s["CRCLEN"] for s in shapes} == {6, 11, 24}
+    assert {s["padCRC"] for s in shapes if s["iIL"]} == {0, 1}
+    assert any(s["rnti"] for s in shapes if s["iIL"]) and any(s["rnti"] for s in shapes if not s["iIL"])
+    assert {s["L"] for s in shapes if s["algo"] == "SCL"} >= {3, 5, 7, 12}
+    assert max(s["K"] for s in shapes) > 211
+    return byN
+
+
+def waterfall_db(K, E):
+    """Es/N0 in dB (noise variance per real sample = 1 / snr, as the fixtures' generator defines it) at
+    which a binary-input AWGN channel's capacity equals K / E: J-function fit of ten Brink et al."""
+    lo, hi = -20.0, 20.0
+    for _ in range(40):
+        mid = (lo + hi) / 2
+        s = 2.0 * 10 ** (mid / 20)   # standard deviation of the channel LLR
+        cap = (1 - 2 ** (-0.3073 * s ** (2 * 0.8935))) ** 1.1064
+        lo, hi = (mid, hi) if cap < K / E else (lo, mid)
+    return lo
+
+
+def channel_llr(rng, bits, snr_db):
+    sigma = 10 ** (-snr_db / 20)
+    return 2 * ((1 - 2.0 * np.asarray(bits)) + rng.normal(0, sigma, len(bits))) / sigma ** 2
+
+
+# E = 8192 where the smallest N admits it (K <= 32 gives N = 256: N = 32 and 64 end at E = 36 and 72), the
+# triangular E = T(T+1)/2 of the channel interleaver, K = 1023, and the longest E of N = 32 and 64
+LIVE_FORCED = ((20, 8192, 10), (31, 8192, 10), (64, 8192, 9), (1023, 8192, 10), (100, 2080, 9), (300, 8128, 10),
+               (1023, 1030, 10), (20, 36, 10), (40, 72, 9), (18, 36, 10), (32, 72, 10))
+LIVE_SEED, LIVE_PER_N = 38212, 19
+FIXTURE_SEED = 5341
+
+
+def live_shapes():
+    return sweep_shapes(LIVE_SEED, LIVE_PER_N, 8192, 16, LIVE_FORCED)
+
+
+def fixture_shapes(per_N):
+    """K <= 151 for DL: the reference's distributed-CRC table overflows int8 from K - 24 = 128 under numpy 2."""
+    return sweep_shapes(FIXTURE_SEED, per_N, 2048, 8, Kdl=151)
+
+
+def load_sweep(path):
+    """tests/golden/polar_golden_sweep.npz -> [(meta dict, llr float64[E], ck int8[K])]."""
+    d = np.load(path)
+    meta = json.loads(str(d["meta"]))
+    q, ck = d["q"], d["ck"]
+    out, a, b = [], 0, 0
+    for c in meta:
+        out.append((c, q[a:a + c["E"]].astype(np.float64) / 4.0, ck[b:b + c["K"]]))
+        a, b = a + c["E"], b + c["K"]
+    assert a == q.size and b == ck.size
+    return out

@@ -38,6 +38,7 @@ def dec():
 
 
 N_DECODE = len(json.loads(str(load("decode")["meta"])))
+SWEEP = R.load_sweep(os.path.join(GOLD, "polar_golden_sweep.npz"))
 
 
 def test_tables_are_permutations():
@@ -122,6 +123,59 @@ def test_restatement_decode(dec, i):
     assert int(st) == c["status"] and np.array_equal(ck, d[f"ck{i}"])
     assert pm == float.fromhex(c["pm"]) and {k: int(v) for k, v in info.items()} == c["info"]
     assert st or (np.all(ck == -1) and math.isinf(pm))
+
+
+@pytest.mark.parametrize("i", range(len(SWEEP)))
+def test_restatement_sweep(i):
+    """polar_ref reproduces the reference's (ck, status) of every recorded sweep case, and its own pm and classes."""
+    c, llr, want = SWEEP[i]
+    rr = R.rate_recover(llr, c["K"], c["N"], c["iBIL"], 20.0, reference_repetition=True)
+    ck, st, pm, info = R.decode(c["algo"], rr, c["E"], c["K"], c["L"], c["nMax"], c["iIL"], c["CRCLEN"], c["padCRC"],
+                                c["rnti"])
+    assert int(st) == c["status"] and ck.dtype == want.dtype and np.array_equal(ck, want)
+    assert pm == float.fromhex(c["pm"]) and {k: int(v) for k, v in info.items()} == c["info"]
+    assert st or (np.all(ck == -1) and math.isinf(pm))
+
+
+def test_sweep_fixture_is_the_committed_shape_list():
+    meta = [c for c, _, _ in SWEEP]
+    assert len(meta) == 960 and all(len(llr) == c["E"] <= 2048 for c, llr, _ in SWEEP)
+    shapes = R.fixture_shapes(160)   # recorded round robin over the six N
+    assert [{k: c[k] for k in R.SWEEP_FIELDS} for c in meta] == [shapes[n * 160 + r] for r in range(160) for n in range(6)]
+    byN = R.sweep_coverage(meta)
+    for N, lst in byN.items():
+        st = [c["status"] for c in lst]
+        assert len(st) == 160 and sum(st) >= 3 and len(st) - sum(st) >= 3, N
+    for k in ("early", "crc_fail", "not_best", "pc_kills", "median_ties", "crc_kills"):
+        assert sum(1 for c in meta if c["info"][k]) >= 3, k
+    assert {(c["nMax"], c["iBIL"]) for c in meta} == {(9, 0), (9, 1), (10, 0), (10, 1)}
+
+
+PLAN_LISTS = {"fixture": [c for c, _, _ in SWEEP], "live": R.live_shapes()}
+
+
+@pytest.mark.parametrize("which,N", [(w, N) for w in PLAN_LISTS for N in (32, 64, 128, 256, 512, 1024)])
+def test_plan_maps_of_every_sweep_shape(which, N):
+    """F, qPC, cksrc, crc_mask, il, mode and N of the C plan equal the restatement's, for every shape the GPU
+    sweeps use (the live list holds the triangular E = 2080 and 8128, and E = 8192)."""
+    shapes = [s for s in PLAN_LISTS[which] if 1 << R.n_value(s["K"], s["E"], s["nMax"]) == N]
+    assert len(shapes) >= 8
+    if which == "live":
+        assert {s["E"] for s in PLAN_LISTS[which]} >= {2080, 8128, 8192}
+    for s in shapes:
+        K, E = s["K"], s["E"]
+        p = polar.Plan(polar.plan_blob(*R.plan_args(s)))
+        lay = R.layout(*R.plan_args(s))
+        assert (p.N, p.nPC, p.nPCwm) == (N, lay["nPC"], lay["nPCwm"]) == (lay["N"], p.nPC, p.nPCwm), s
+        assert np.array_equal(p.F, lay["F"]) and p.qPC.tolist() == lay["qPC"].tolist(), s
+        hdr = p.blob[:128].view(np.int32)
+        assert np.array_equal(p.blob[hdr[21]:hdr[21] + 2 * K].view(np.int16), lay["ck_src"]), s
+        assert p.mode_name[:3] == lay["mode"][:3], s
+        want = lay["crc_mask"].tolist() if s["iIL"] else [0] * 24
+        assert [(int(hdr[18]) >> c) & 1 for c in range(24)] == want, s
+        il = R.chan_il(E)
+        assert np.array_equal(p.blob[hdr[27]:hdr[27] + 2 * E].view(np.int16), il), s
+        assert np.array_equal(p.blob[hdr[28]:hdr[28] + 2 * E].view(np.int16), np.argsort(il)), s
 
 
 # ------------------------------------------------------------------------------------- refusals
