@@ -6,12 +6,14 @@ the hot path.  There is no CPU fallback: if the library or a GPU is missing, cal
 import collections
 import ctypes
 import os
+import re
 import threading
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDPC5G_LIB") or os.path.join(HERE, "libldpc5g.so")
+HEADER = os.path.join(os.path.dirname(HERE), "include", "ldpc5g.h")
 
 F64, F32 = 0, 1
 FLOODING, LAYERED = 0, 1
@@ -27,195 +29,48 @@ ML_ALGO = {"ML-soft": (0, 0), "ML-IRC-soft": (0, 1), "ML-hard": (1, 0), "ML-IRC-
 # CE_config["CE_algo"] (nr_channel_estimation.py:117-124) -> LDPC5G_CE_*
 CE_ALGO = {"DFT": 0, "DCT": 1, "DFT_symmetric": 2, "DCT_symmetric": 3}
 
-# every symbol include/ldpc5g.h declares: name -> (restype, argtypes)
-_c = ctypes
-OPTIONAL = {"ldpc5g_dec_blocks_per_cu", "ldpc5g_split_timeouts"}
-SIGNATURES = {
-    "ldpc5g_find_ils": (_c.c_int, [_c.c_int32]),
-    "ldpc5g_dec_blocks_per_cu": (_c.c_int, [_c.c_int32, _c.c_int32, _c.c_int32]),
-    "ldpc5g_encode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
-                                 _c.c_int64, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_decode_ms": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_void_p,
-                                    _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_double,
-                                    _c.c_double, _c.c_int32, _c.c_int32, _c.c_int64, _c.c_int64,
-                                    _c.c_void_p]),
-    "ldpc5g_decode_ms_host": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
-                                         _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                         _c.c_double, _c.c_double, _c.c_int32, _c.c_void_p]),
-    "ldpc5g_encode_host": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
-                                      _c.c_void_p]),
-    "ldpc5g_decode_ms_mixed": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int32,
-                                          _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int32,
-                                          _c.c_double, _c.c_double, _c.c_int32, _c.c_int32,
-                                          _c.c_void_p]),
-    "ldpc5g_mixed_plan": (_c.c_int64, [_c.c_void_p, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_int64]),
-    "ldpc5g_decode_ms_mixed_plan": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int32,
-                                               _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int32,
-                                               _c.c_double, _c.c_double, _c.c_int32, _c.c_int32,
-                                               _c.c_void_p]),
-    "ldpc5g_decode_bf": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_void_p,
-                                    _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                    _c.c_int64, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_bp_scratch_elems": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32]),
-    "ldpc5g_decode_bp": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
-                                    _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                    _c.c_int32, _c.c_int64, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_sparse_scratch_bytes": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                                 _c.c_int32]),
-    "ldpc5g_decode_sparse": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32,
-                                        _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_void_p,
-                                        _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_int32,
-                                        _c.c_double, _c.c_double, _c.c_void_p, _c.c_int64,
-                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
-                                        _c.c_void_p]),
-    "ldpc5g_crc": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32,
-                              _c.c_void_p, _c.c_void_p]),
-    "ldpc5g_sch_config": (_c.c_int, [_c.c_int32, _c.c_int32, _c.c_double, _c.c_int32, _c.c_int32,
-                                     _c.c_int64, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_sch_segment": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int32, _c.c_void_p,
-                                      _c.c_void_p, _c.c_void_p]),
-    "ldpc5g_sch_ratematch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_void_p,
-                                        _c.c_void_p, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_sch_encode": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                     _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_void_p,
-                                     _c.c_void_p]),
-    "ldpc5g_sch_raterecover": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p,
-                                          _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_int32,
-                                          _c.c_void_p]),
-    "ldpc5g_sch_tb_check": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int32,
-                                       _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p,
-                                       _c.c_void_p, _c.c_void_p]),
-    "ldpc5g_sch_decode": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p, _c.c_int32,
-                                     _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_void_p,
-                                     _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_double,
-                                     _c.c_double, _c.c_int32, _c.c_void_p, _c.c_int64,
-                                     _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
-    "ldpc5g_sch_demod_raterecover": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p,
-                                                _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
-                                                _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p,
-                                                _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_sch_rx_scratch_elems": (_c.c_int64, [_c.c_void_p, _c.c_int32, _c.c_int32]),
-    "ldpc5g_sch_rx_decode": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p,
-                                        _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
-                                        _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p,
-                                        _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                        _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_double,
-                                        _c.c_double, _c.c_int32, _c.c_void_p, _c.c_int64,
-                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
-    "ldpc5g_sch_multi_sizes": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_void_p]),
-    "ldpc5g_sch_encode_multi": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
-                                           _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p,
-                                           _c.c_void_p, _c.c_void_p]),
-    "ldpc5g_sch_raterecover_multi": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p,
-                                                _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_int32,
-                                                _c.c_void_p]),
-    "ldpc5g_sch_multi_plan": (_c.c_int64, [_c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int64]),
-    "ldpc5g_sch_raterecover_multi_plan": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int32,
-                                                     _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int32,
-                                                     _c.c_void_p]),
-    "ldpc5g_sch_decode_multi": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p,
-                                           _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_int32,
-                                           _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int32,
-                                           _c.c_double, _c.c_double, _c.c_int32, _c.c_void_p,
-                                           _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
-                                           _c.c_void_p]),
-    "ldpc5g_prbs": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p, _c.c_int64,
-                               _c.c_void_p]),
-    "ldpc5g_scramble_modulate": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
-                                            _c.c_int32, _c.c_int64, _c.c_int32, _c.c_void_p,
-                                            _c.c_int64, _c.c_void_p]),
-    "ldpc5g_demod_descramble": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p,
-                                           _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
-                                           _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int32,
-                                           _c.c_int64, _c.c_void_p]),
-    "ldpc5g_equalize": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                   _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64,
-                                   _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                   _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_ml_detect": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                    _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64,
-                                    _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                    _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                    _c.c_int32, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                    _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_ce_workspace_bytes": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                               _c.c_int32, _c.c_int32]),
-    "ldpc5g_channel_estimate": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32,
-                                           _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                           _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
-                                           _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                           _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
-                                           _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
-                                           _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
-                                           _c.c_void_p, _c.c_void_p]),
-    "ldpc5g_to_compensate": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
-                                        _c.c_void_p, _c.c_int32, _c.c_int64, _c.c_int64, _c.c_int32,
-                                        _c.c_int32, _c.c_void_p]),
-    "ldpc5g_slot_rx_frontend": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int32,
-                                           _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                           _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32,
-                                           _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
-                                           _c.c_void_p]),
-    "ldpc5g_slot_map": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                   _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                   _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
-                                   _c.c_void_p, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_transform_precode": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32,
-                                            _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p]),
-    "ldpc5g_low_papr_seq": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_double, _c.c_int32,
-                                       _c.c_void_p, _c.c_void_p]),
-    "ldpc5g_slot_rx_frontend_tp": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int32,
-                                              _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                              _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_void_p,
-                                              _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_slot_map_tp": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                      _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                      _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32,
-                                      _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_ofdm_demod": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int64,
-                                     _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                     _c.c_int64, _c.c_void_p]),
-    "ldpc5g_ofdm_mod": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64,
-                                   _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                   _c.c_int32, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_polar_plan": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                       _c.c_int32, _c.c_void_p, _c.c_int64]),
-    "ldpc5g_polar_encode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
-                                       _c.c_int32, _c.c_void_p]),
-    "ldpc5g_polar_rate_match": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                           _c.c_int64, _c.c_int32, _c.c_int32, _c.c_void_p]),
-    "ldpc5g_polar_rate_recover": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                             _c.c_int64, _c.c_int32, _c.c_int32, _c.c_double, _c.c_int32,
-                                             _c.c_void_p]),
-    "ldpc5g_polar_decode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
-                                       _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p]),
-    "ldpc5g_uci_rm_info": (_c.c_int, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
-                                      _c.c_double, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32,
-                                      _c.c_int32, _c.c_int32, _c.c_double, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_uci_map_plan": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int32,
-                                         _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int64,
-                                         _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64]),
-    "ldpc5g_uci_mux": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
-                                  _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p]),
-    "ldpc5g_uci_demux": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_int64, _c.c_void_p, _c.c_int64,
-                                    _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
-                                    _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p]),
-    "ldpc5g_uci_scramble_modulate": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
-                                                _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_void_p]),
-    "ldpc5g_smallblock_encode": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_int64,
-                                            _c.c_int32, _c.c_int32, _c.c_void_p]),
-    "ldpc5g_smallblock_decode": (_c.c_int, [_c.c_void_p, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32,
-                                            _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p]),
-    "ldpc5g_pack_records": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
-                                       _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
-                                       _c.c_void_p]),
-    "ldpc5g_unpack_records": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int64,
-                                         _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p,
-                                         _c.c_int64, _c.c_void_p]),
-    "ldpc5g_split_timeouts": (_c.c_int, [_c.c_void_p]),
-    "ldpc5g_last_error": (_c.c_char_p, []),
-    "ldpc5g_version": (_c.c_char_p, []),
-}
+OPTIONAL = {"ldpc5g_dec_blocks_per_cu", "ldpc5g_split_timeouts"}   # absent from older libraries
+
+_RESTYPE = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
+_ARGTYPE = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+            "int": ctypes.c_int, "double": ctypes.c_double, "float": ctypes.c_float}
+
+
+def _parse_header(path):
+    """Every `ldpc5g_*` prototype of the header -> (SIGNATURES, PARAMS).  Any pointer parameter is a
+    c_void_p (struct pointers included).  A prototype or a type outside the two tables above raises
+    and names the line: nothing is guessed."""
+    with open(path) as f:
+        src = f.read()
+    def blank(m):   # keep offsets, so line numbers stay true
+        return re.sub(r"[^\n]", " ", m.group())
+    src = re.sub(r"//[^\n]*", blank, re.sub(r"/\*.*?\*/", blank, src, flags=re.S))
+    sigs, params = {}, {}
+    for m in re.finditer(r"\b(int|int64_t|const\s+char\s*\*)\s*(ldpc5g_\w+)\s*\(([^()]*)\)\s*;", src):
+        where = f"{path}:{src.count(chr(10), 0, m.start(2)) + 1}: {m.group(2)}"
+        argtypes, names = [], []
+        plist = m.group(3).strip()
+        for p in ([] if plist == "void" else plist.split(",")):
+            pm = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\*?)\s*(\w+)\s*", p)
+            if not pm or not (pm.group(2) or pm.group(1) in _ARGTYPE):
+                raise ImportError(f"{where}: parameter {p.strip()!r} has no ctypes mapping")
+            argtypes.append(ctypes.c_void_p if pm.group(2) else _ARGTYPE[pm.group(1)])
+            names.append(pm.group(3))
+        sigs[m.group(2)] = (_RESTYPE[re.sub(r"\s+", " ", m.group(1)).replace(" *", "*")], argtypes)
+        params[m.group(2)] = tuple(names)
+    for m in re.finditer(r"\b(ldpc5g_\w+)\s*\(", src):
+        if m.group(1) not in sigs:
+            raise ImportError(f"{path}:{src.count(chr(10), 0, m.start()) + 1}: {m.group(1)}: "
+                              "not a prototype `int | int64_t | const char* name(params);`")
+    return sigs, params
+
+
+# every function include/ldpc5g.h declares: name -> (restype, argtypes), name -> parameter names
+SIGNATURES, PARAMS = _parse_header(HEADER)
+# per function, resolved once: indices of the pointer parameters; whether `stream` comes last
+_POINTERS = {n: tuple(i for i, a in enumerate(args) if a is ctypes.c_void_p)
+             for n, (_, args) in SIGNATURES.items()}
+_STREAMED = {n for n, p in PARAMS.items() if p[-1:] == ("stream",)}
 
 
 class CbDesc(ctypes.Structure):
@@ -253,15 +108,99 @@ def lib():
             raise LdpcLibError(
                 f"{LIB_PATH} is missing: build it with `python -m python_5gtoolbox_amd.build` "
                 "(there is no CPU fallback for the LDPC hot path)")
-        h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            if name in OPTIONAL and not hasattr(h, name):
-                continue   # diagnostics absent from an older library (A/B builds)
-            f = getattr(h, name)
-            f.restype = res
-            f.argtypes = args
-        _lib = h
+        _lib = bind(ctypes.CDLL(LIB_PATH))
     return _lib
+
+
+def bind(handle):
+    """Set restype / argtypes of every declared function on a CDLL and return it."""
+    for name, (res, args) in SIGNATURES.items():
+        if name in OPTIONAL and not hasattr(handle, name):
+            continue   # diagnostics absent from an older library (A/B builds)
+        f = getattr(handle, name)
+        f.restype = res
+        f.argtypes = args
+    return handle
+
+
+def invoke(name, **kw):
+    """Call the library function `name` with its arguments by the header's parameter names and
+    return the raw result.  kw must hold exactly PARAMS[name]: anything else is a TypeError before
+    the library is entered.  Pointer parameters take a torch tensor (data_ptr()), a numpy array
+    (.ctypes.data), None, an int or a ctypes object (byref, array, c_void_p); the other parameters
+    pass through unchanged."""
+    return _invoke(name, kw)
+
+
+def _address(a):
+    """Address of a numpy array's first element.  a.ctypes.data builds an object per call (about
+    1 us, a third of a whole drop-in call's marshalling); a ctypes view of the buffer costs a third
+    of that, but exists only for writable, contiguous, non-empty arrays."""
+    try:
+        return ctypes.addressof(ctypes.c_char.from_buffer(a))
+    except (TypeError, ValueError, BufferError):
+        return a.ctypes.data
+
+
+def _invoke(name, kw):
+    names = PARAMS[name]
+    try:
+        args = [kw[n] for n in names]
+    except KeyError:
+        args = None
+    if args is None or len(kw) != len(names):
+        raise TypeError(f"{name}: missing {sorted(set(names) - set(kw))}, "
+                        f"unexpected {sorted(set(kw) - set(names))}")
+    for i in _POINTERS[name]:
+        v = args[i]
+        if v is not None and type(v) is not int:
+            if isinstance(v, np.ndarray):
+                args[i] = _address(v)
+            else:
+                p = getattr(v, "data_ptr", None)
+                if p is not None:
+                    args[i] = p()
+    return getattr(lib(), name)(*args)
+
+
+def call(name, device=None, **kw):
+    """invoke() in the frame every wrapper repeats: under torch.cuda.device(device) when one is
+    given, with the current stream of `device` for a trailing `stream` the caller left out, and
+    with the result through check().  Returns None for an `int` status and the value of an
+    `int64_t` size (negative: check() raises)."""
+    if device is None:
+        if "stream" not in kw and name in _STREAMED:
+            kw["stream"] = torch().cuda.current_stream().cuda_stream
+        rc = _invoke(name, kw)
+    else:
+        t = torch()
+        with t.cuda.device(device):
+            if "stream" not in kw and name in _STREAMED:
+                kw["stream"] = t.cuda.current_stream(device).cuda_stream
+            rc = _invoke(name, kw)
+    res = SIGNATURES[name][0]
+    if res is ctypes.c_int:
+        return check(rc)
+    if res is ctypes.c_int64 and rc < 0:
+        check(rc)
+    return rc
+
+
+def row_stride(x, d, row):
+    """Stride of dimension d of x for the ABI's ld* arguments; the stride of a size-1 dimension is
+    arbitrary in torch (and unused by the library), so `row`, the dense value, stands in for it."""
+    return x.stride(d) if x.shape[d] > 1 else row
+
+
+def dtype_id(dt, llr=False):
+    """LDPC5G_F32 / LDPC5G_F64 of a real or complex torch dtype; llr=True accepts only the real two."""
+    t = torch()
+    if dt == t.float32 or (dt == t.complex64 and not llr):
+        return F32
+    if dt == t.float64 or (dt == t.complex128 and not llr):
+        return F64
+    raise AssertionError("LLRs must be float32 or float64" if llr else
+                         f"dtype {dt}: float32 / float64 or complex64 / complex128")
 
 
 def check(rc):
@@ -364,5 +303,5 @@ def split_timeouts():
     """Codeblocks of the current device whose multi-workgroup float64 decode gave up waiting for
     its parts to be co-resident (status 0, iters -1; include/ldpc5g.h ldpc5g_split_timeouts)."""
     n = ctypes.c_uint32(0)
-    check(lib().ldpc5g_split_timeouts(ctypes.byref(n)))
+    call("ldpc5g_split_timeouts", count=ctypes.byref(n))
     return int(n.value)

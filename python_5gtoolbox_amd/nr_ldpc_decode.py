@@ -67,7 +67,7 @@ def nr_decode_ldpc_batch(LLR, Zc, bgn, L, algo="min-sum", alpha=1.0, beta=0.0,
     assert x.shape[1] == (Nf if full else N), f"LLR rows must hold {Nf if full else N} values"
     if x.stride(1) != 1:
         x = x.contiguous()
-    dt = _lib.F64 if x.dtype == t.float64 else _lib.F32
+    dt = _lib.dtype_id(x.dtype)
     if out is None:
         ck = t.empty((B, Nf), dtype=t.int8, device=x.device)
         st = t.empty((B,), dtype=t.uint8, device=x.device)
@@ -82,26 +82,19 @@ def nr_decode_ldpc_batch(LLR, Zc, bgn, L, algo="min-sum", alpha=1.0, beta=0.0,
         assert ck.device == x.device and st.device == x.device and it.device == x.device, \
             "outputs must live on the LLR tensor's device"
     flags = (_lib.LLR_FULL if full else 0) | (_lib.RATE_MATCHED if rate_matched else 0)
-    lib = _lib.lib()
-    with t.cuda.device(x.device):
-        stream = _lib.stream_ptr(x.device)
-        if algo == "min-sum":
-            _lib.check(lib.ldpc5g_decode_ms(
-                _lib.ptr(x), dt, _lib.ptr(ck), _lib.ptr(st), _lib.ptr(it), B, bgn, Zc, int(L),
-                float(alpha), float(beta), SCHEDULES[schedule], flags, x.stride(0), ck.stride(0),
-                stream))
-        elif algo == "BF":
-            _lib.check(lib.ldpc5g_decode_bf(
-                _lib.ptr(x), dt, _lib.ptr(ck), _lib.ptr(st), _lib.ptr(it), B, bgn, Zc, int(L),
-                flags, x.stride(0), ck.stride(0), stream))
-        else:   # BP: float64 sum-product with a per-edge message scratch
-            if x.dtype != t.float64:
-                x = x.double()
-            n = lib.ldpc5g_bp_scratch_elems(B, bgn, Zc)
-            scratch = t.empty((max(n, 1),), dtype=t.float64, device=x.device)
-            _lib.check(lib.ldpc5g_decode_bp(
-                _lib.ptr(x), _lib.ptr(ck), _lib.ptr(st), _lib.ptr(it), _lib.ptr(scratch), n, B,
-                bgn, Zc, int(L), flags, x.stride(0), ck.stride(0), stream))
+    if algo == "BP" and x.dtype != t.float64:   # float64 sum-product
+        x = x.double()
+    common = dict(ck=ck, status=st, iters=it, B=B, bgn=bgn, Zc=Zc, L=int(L), flags=flags, ldl=x.stride(0),
+                  ldc=ck.stride(0))
+    if algo == "min-sum":
+        _lib.call("ldpc5g_decode_ms", x.device, llr=x, llr_dtype=dt, alpha=float(alpha), beta=float(beta),
+                  schedule=SCHEDULES[schedule], **common)
+    elif algo == "BF":
+        _lib.call("ldpc5g_decode_bf", x.device, llr=x, llr_dtype=dt, **common)
+    else:   # BP: a per-edge message scratch
+        n = _lib.invoke("ldpc5g_bp_scratch_elems", B=B, bgn=bgn, Zc=Zc)
+        scratch = t.empty((max(n, 1),), dtype=t.float64, device=x.device)
+        _lib.call("ldpc5g_decode_bp", x.device, llr=x, scratch=scratch, scratch_elems=n, **common)
     if is_np:
         return ck.cpu().numpy(), st.cpu().numpy().astype(bool), it.cpu().numpy()
     return ck, st, it
@@ -123,9 +116,8 @@ def _decode_one(LLRin, Zc, bgn, L, algo, alpha, beta, full):
         # rows at high code rates) enables dead-row skipping: same results, less work
         rm = not x[-Zc:].view(np.int64).any()
         flags = (_lib.LLR_FULL if full else 0) | (_lib.RATE_MATCHED if rm else 0)
-        _lib.check(_lib.lib().ldpc5g_decode_ms_host(
-            x.ctypes.data, ck.ctypes.data, st.ctypes.data, it.ctypes.data, 1, bgn, Zc, int(L),
-            float(alpha), float(beta), flags, _lib.stream_ptr()))
+        _lib.call("ldpc5g_decode_ms_host", llr=x, ck=ck, status=st, iters=it, B=1, bgn=bgn, Zc=Zc, L=int(L),
+                  alpha=float(alpha), beta=float(beta), flags=flags)
         if it[0] < 0:   # the multi-workgroup kernel gave up waiting for co-resident parts
             raise _lib.LdpcLibError("nr_decode_ldpc: the multi-workgroup decode timed out waiting for "
                                     "its workgroups to be co-resident (include/ldpc5g.h, "
@@ -281,16 +273,13 @@ def decode_ldpc_batch(LLR, H, L, algo="min-sum", alpha=1.0, beta=0.0, out=None):
         assert ck.dtype == t.int8 and ck.dim() == 2 and ck.shape[0] == B and ck.shape[1] >= N \
             and ck.stride(1) == 1 and st.dtype == t.uint8 and it.dtype == t.int32 \
             and st.numel() >= B and it.numel() >= B and st.is_contiguous() and it.is_contiguous()
-    lib = _lib.lib()
-    nsc = lib.ldpc5g_sparse_scratch_bytes(B, g.M, g.N, g.E, a)
+    nsc = _lib.invoke("ldpc5g_sparse_scratch_bytes", B=B, M=g.M, N=g.N, E=g.E, algo=a)
     assert nsc >= 0
     scratch = t.empty((max(nsc, 1),), dtype=t.uint8, device=x.device)
-    with t.cuda.device(x.device):
-        _lib.check(lib.ldpc5g_decode_sparse(
-            _lib.ptr(x), x.stride(0), B, g.M, g.N, g.E, _lib.ptr(g.row_ptr), _lib.ptr(g.col_idx),
-            _lib.ptr(g.col_ptr), _lib.ptr(g.col_edge), _lib.ptr(g.col_row), int(L), a,
-            float(alpha), float(beta), _lib.ptr(ck), ck.stride(0), _lib.ptr(st), _lib.ptr(it),
-            _lib.ptr(scratch), nsc, _lib.stream_ptr(x.device)))
+    _lib.call("ldpc5g_decode_sparse", x.device, llr=x, ldl=x.stride(0), B=B, M=g.M, N=g.N, E=g.E, row_ptr=g.row_ptr,
+              col_idx=g.col_idx, col_ptr=g.col_ptr, col_edge=g.col_edge, col_row=g.col_row, L=int(L), algo=a,
+              alpha=float(alpha), beta=float(beta), ck=ck, ldc=ck.stride(0), status=st, iters=it, scratch=scratch,
+              scratch_bytes=nsc)
     if is_np:
         return ck.cpu().numpy(), st.cpu().numpy().astype(bool), it.cpu().numpy()
     return ck, st, it

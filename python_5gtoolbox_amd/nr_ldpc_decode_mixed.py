@@ -34,12 +34,10 @@ def decode_mixed(items, L, alpha=1.0, beta=0.0, schedule="flooding", rate_matche
     ck = t.empty(max(co, 1), dtype=t.int8, device=x.device)
     st = t.empty(max(B, 1), dtype=t.uint8, device=x.device)
     it = t.empty(max(B, 1), dtype=t.int32, device=x.device)
-    with t.cuda.device(x.device):
-        _lib.check(_lib.lib().ldpc5g_decode_ms_mixed(
-            desc, B, _lib.ptr(x), _lib.F64 if f64 else _lib.F32, _lib.ptr(ck), _lib.ptr(st),
-            _lib.ptr(it), int(L), float(alpha), float(beta),
-            _lib.LAYERED if schedule == "layered" else _lib.FLOODING,
-            _lib.RATE_MATCHED if rate_matched else 0, _lib.stream_ptr(x.device)))
+    _lib.call("ldpc5g_decode_ms_mixed", x.device, desc=desc, B=B, llr_base=x, llr_dtype=_lib.F64 if f64 else _lib.F32,
+              ck_base=ck, status=st, iters=it, L=int(L), alpha=float(alpha), beta=float(beta),
+              schedule=_lib.LAYERED if schedule == "layered" else _lib.FLOODING,
+              flags=_lib.RATE_MATCHED if rate_matched else 0)
     ckh = ck.cpu().numpy()
     return ([ckh[c:c + n].copy() for _, c, n in rows], st.cpu().numpy()[:B].astype(bool),
             it.cpu().numpy()[:B])
@@ -62,8 +60,7 @@ class MixedBatch:
         parts, lo, co, k = [], 0, 0, 0
         self.rows = []
         dt = groups[0][2].dtype
-        assert dt in (t.float32, t.float64), "LLRs must be float32 or float64"
-        self.dtype = _lib.F32 if dt == t.float32 else _lib.F64
+        self.dtype = _lib.dtype_id(dt, llr=True)
         for bgn, Zc, llr in groups:
             assert bgn in [1, 2] and find_iLS(Zc) < 8 and llr.dtype == dt
             K, N, Nf = code_dims(bgn, Zc)
@@ -94,12 +91,10 @@ class MixedBatch:
         p = self._plans.get(schedule)
         if p is None:
             t = _lib.torch()
-            lib = _lib.lib()
             sc = _lib.LAYERED if schedule == "layered" else _lib.FLOODING
-            n = lib.ldpc5g_mixed_plan(self.desc, self.B, sc, None, 0)
-            _lib.check(int(min(n, 0)))
+            n = _lib.call("ldpc5g_mixed_plan", desc=self.desc, B=self.B, schedule=sc, plan=None, plan_bytes=0)
             host = t.empty((max(n, 1),), dtype=t.uint8, pin_memory=True)
-            _lib.check(int(min(lib.ldpc5g_mixed_plan(self.desc, self.B, sc, _lib.ptr(host), n), 0)))
+            _lib.call("ldpc5g_mixed_plan", desc=self.desc, B=self.B, schedule=sc, plan=host, plan_bytes=n)
             dev = host.to(self.llr.device, non_blocking=True)
             p = self._plans[schedule] = (host, dev)
         return p
@@ -108,13 +103,10 @@ class MixedBatch:
         """<= 2 kernel launches on the current stream, asynchronous (no host synchronisation);
         returns the device buffers (ck flat, status (B,), iters (B,)).  rate_matched: see
         decode_mixed."""
-        t = _lib.torch()
         assert schedule != "layered" or self.dtype == _lib.F32, "the layered kernel is float32"
         host, dev = self._plan(schedule)
-        with t.cuda.device(self.llr.device):
-            _lib.check(_lib.lib().ldpc5g_decode_ms_mixed_plan(
-                _lib.ptr(dev), _lib.ptr(host), _lib.ptr(self.llr), self.dtype, _lib.ptr(self.ck),
-                _lib.ptr(self.status), _lib.ptr(self.iters), int(L), float(alpha), float(beta),
-                _lib.LAYERED if schedule == "layered" else _lib.FLOODING,
-                _lib.RATE_MATCHED if rate_matched else 0, _lib.stream_ptr(self.llr.device)))
+        _lib.call("ldpc5g_decode_ms_mixed_plan", self.llr.device, plan_dev=dev, plan_host=host, llr_base=self.llr,
+                  llr_dtype=self.dtype, ck_base=self.ck, status=self.status, iters=self.iters, L=int(L),
+                  alpha=float(alpha), beta=float(beta), schedule=_lib.LAYERED if schedule == "layered" else _lib.FLOODING,
+                  flags=_lib.RATE_MATCHED if rate_matched else 0)
         return self.ck, self.status[:self.B], self.iters[:self.B]

@@ -43,9 +43,7 @@ def encode_ldpc_batch(cbs, bgn, out=None):
     if out is None:
         out = t.empty((B, N), dtype=t.int8, device=x.device)
     assert out.dtype == t.int8 and out.shape[0] == B and out.shape[1] >= N and out.stride(1) == 1
-    with t.cuda.device(x.device):
-        _lib.check(_lib.lib().ldpc5g_encode(_lib.ptr(x), _lib.ptr(out), B, bgn, Zc, x.stride(0),
-                                            out.stride(0), _lib.stream_ptr(x.device)))
+    _lib.call("ldpc5g_encode", x.device, ck=x, dn=out, B=B, bgn=bgn, Zc=Zc, ldk=x.stride(0), ldn=out.stride(0))
     if is_np:
         return out[:, :N].cpu().numpy()
     return out
@@ -66,8 +64,7 @@ def encode_ldpc(ck, bgn):
     # staging, one H2D, the launch, one D2H, one synchronisation — no torch op on the way)
     x = np.ascontiguousarray(np.asarray(ck).reshape(-1), dtype=np.int8)
     dn = np.empty(N, np.int8)
-    _lib.check(_lib.lib().ldpc5g_encode_host(x.ctypes.data, dn.ctypes.data, 1, bgn, Zc,
-                                             _lib.stream_ptr()))
+    _lib.call("ldpc5g_encode_host", ck=x, dn=dn, B=1, bgn=bgn, Zc=Zc)
     # reference side effect: fillers of the caller's block are zeroed in place (:34-35)
     tail = ck[2 * Zc:K]
     tail[tail == -1] = 0

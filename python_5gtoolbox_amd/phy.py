@@ -50,9 +50,7 @@ def prbs_words(cinit, nbits, out=None):
     T = c.shape[0]
     nw = (int(nbits) + 31) // 32
     w = out if out is not None else t.empty((T, max(nw, 1)), dtype=t.int32, device=c.device)
-    with t.cuda.device(c.device):
-        _lib.check(_lib.lib().ldpc5g_prbs(_lib.ptr(c), T, int(nbits), _lib.ptr(w), w.stride(0),
-                                          _lib.stream_ptr(c.device)))
+    _lib.call("ldpc5g_prbs", c.device, cinit=c, T=T, nbits=int(nbits), words=w, ldw=w.stride(0))
     return w
 
 
@@ -63,26 +61,16 @@ def scramble_modulate(bits, mod, cinit=None, words=None, out=None):
     assert bits.dim() == 2 and bits.dtype == t.int8 and bits.stride(1) == 1
     T, G = bits.shape
     Qm = bits_per_symbol(mod)
-    w = words if words is not None else (prbs_words(cinit, G) if cinit is not None else None)
+    w = words if words is not None else (None if cinit is None else prbs_words(cinit, G))
     sym = out if out is not None else t.empty((T, G // Qm), dtype=t.complex64, device=bits.device)
-    with t.cuda.device(bits.device):
-        _lib.check(_lib.lib().ldpc5g_scramble_modulate(
-            _lib.ptr(bits), bits.stride(0), _lib.ptr(w) if w is not None else None,
-            w.stride(0) if w is not None else 0, T, G, int(mod), _lib.ptr(sym), sym.stride(0),
-            _lib.stream_ptr(bits.device)))
+    _lib.call("ldpc5g_scramble_modulate", bits.device, bits=bits, ldb=bits.stride(0), prbs=w,
+              ldw=w.stride(0) if w is not None else 0, T=T, nbits=G, mod=int(mod), sym=sym, ldsym=sym.stride(0))
     return sym
 
 
-def equalize(y, h, cov, algo, re_idx=None, re_per_cov=12, out=None):
-    """Linear MIMO equalisation of the data resource elements of T transport blocks
-    (ldpc5g_equalize; ZF.py / MMSE.py through nr_channel_eq.py:12-26).  y: (T, R, Nr), h:
-    (T, R, Nr, NL), cov: (T, ceil(R/re_per_cov), Nr, Nr) complex64 / complex128 device tensors of
-    one dtype (rows may be padded: only stride(0) is free); algo: "ZF", "ZF-IRC", "MMSE" or
-    "MMSE-IRC"; re_idx: (nre,) int32 ascending flat indices of the data REs, None for all R.
-    Returns (sym (T, nre*NL) of the input dtype, noise_var (T, nre*NL) float32), or fills
-    out=(sym, noise_var)."""
-    t = _lib.require_gpu()
-    assert algo in _lib.EQ_ALGO, f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO)}"
+def _mimo_inputs(t, y, h, cov, re_idx, re_per_cov):
+    """The checks of y, h, cov and re_idx that equalize and ml_detect share -> (T, NL, nre, the
+    library arguments y .. NL that ldpc5g_equalize and ldpc5g_ml_detect have in common)."""
     assert y.dim() == 3 and h.dim() == 4 and cov.dim() == 4
     assert y.dtype in (t.complex64, t.complex128) and h.dtype == y.dtype and cov.dtype == y.dtype
     T, R, Nr = y.shape
@@ -95,6 +83,23 @@ def equalize(y, h, cov, algo, re_idx=None, re_per_cov=12, out=None):
         assert re_idx.dim() == 1 and re_idx.dtype == t.int32 and re_idx.is_contiguous()
         assert re_idx.device == y.device
     nre = re_idx.shape[0] if re_idx is not None else R
+    ld = _lib.row_stride
+    return T, NL, nre, dict(y=y, ldy=ld(y, 0, R * Nr), h=h, ldh=ld(h, 0, R * Nr * NL), cov=cov,
+                            ldcov=ld(cov, 0, cov.shape[1] * Nr * Nr), in_dtype=_lib.dtype_id(y.dtype),
+                            re_idx=re_idx, R=R, nre=nre, re_per_cov=int(re_per_cov), T=T, Nr=Nr, NL=NL)
+
+
+def equalize(y, h, cov, algo, re_idx=None, re_per_cov=12, out=None):
+    """Linear MIMO equalisation of the data resource elements of T transport blocks
+    (ldpc5g_equalize; ZF.py / MMSE.py through nr_channel_eq.py:12-26).  y: (T, R, Nr), h:
+    (T, R, Nr, NL), cov: (T, ceil(R/re_per_cov), Nr, Nr) complex64 / complex128 device tensors of
+    one dtype (rows may be padded: only stride(0) is free); algo: "ZF", "ZF-IRC", "MMSE" or
+    "MMSE-IRC"; re_idx: (nre,) int32 ascending flat indices of the data REs, None for all R.
+    Returns (sym (T, nre*NL) of the input dtype, noise_var (T, nre*NL) float32), or fills
+    out=(sym, noise_var)."""
+    t = _lib.require_gpu()
+    assert algo in _lib.EQ_ALGO, f"algo {algo!r}: one of {sorted(_lib.EQ_ALGO)}"
+    T, NL, nre, args = _mimo_inputs(t, y, h, cov, re_idx, re_per_cov)
     if out is not None:
         sym, nv = out
         assert sym.dtype == y.dtype and sym.shape == (T, nre * NL) and sym.stride(1) == 1
@@ -102,15 +107,8 @@ def equalize(y, h, cov, algo, re_idx=None, re_per_cov=12, out=None):
     else:
         sym = t.empty((T, nre * NL), dtype=y.dtype, device=y.device)
         nv = t.empty((T, nre * NL), dtype=t.float32, device=y.device)
-    def ld(x, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
-        return x.stride(0) if T > 1 else row
-    with t.cuda.device(y.device):
-        _lib.check(_lib.lib().ldpc5g_equalize(
-            _lib.ptr(y), ld(y, R * Nr), _lib.ptr(h), ld(h, R * Nr * NL), _lib.ptr(cov),
-            ld(cov, cov.shape[1] * Nr * Nr), _lib.F32 if y.dtype == t.complex64 else _lib.F64,
-            _lib.ptr(re_idx) if re_idx is not None else None, R, nre, int(re_per_cov), T, Nr, NL,
-            _lib.EQ_ALGO[algo], _lib.ptr(sym), ld(sym, nre * NL), _lib.ptr(nv), ld(nv, nre * NL),
-            _lib.stream_ptr(y.device)))
+    _lib.call("ldpc5g_equalize", y.device, **args, algo=_lib.EQ_ALGO[algo], sym=sym,
+              ldsym=_lib.row_stride(sym, 0, nre * NL), noise_var=nv, ldnv=_lib.row_stride(nv, 0, nre * NL))
     return sym, nv
 
 
@@ -129,41 +127,21 @@ def ml_detect(y, h, cov, mod, algo, re_idx=None, re_per_cov=12, cinit=None, word
     t = _lib.require_gpu()
     assert algo in _lib.ML_ALGO, f"algo {algo!r}: one of {sorted(_lib.ML_ALGO)}"
     assert all(w in ("sym", "noise_var", "hardbits") for w in want), want
-    assert y.dim() == 3 and h.dim() == 4 and cov.dim() == 4
-    assert y.dtype in (t.complex64, t.complex128) and h.dtype == y.dtype and cov.dtype == y.dtype
-    T, R, Nr = y.shape
-    NL = h.shape[3]
+    T, NL, nre, args = _mimo_inputs(t, y, h, cov, re_idx, re_per_cov)
     Qm = bits_per_symbol(mod)
-    ncov = (R + int(re_per_cov) - 1) // int(re_per_cov) if re_per_cov >= 1 else 0
-    assert h.shape == (T, R, Nr, NL) and cov.shape[0] == T and cov.shape[1] >= ncov and cov.shape[2:] == (Nr, Nr)
-    assert y[0].is_contiguous() and h[0].is_contiguous() and cov[0].is_contiguous(), \
-        "only the transport-block stride is free"
-    if re_idx is not None:
-        assert re_idx.dim() == 1 and re_idx.dtype == t.int32 and re_idx.is_contiguous()
-        assert re_idx.device == y.device
-    nre = re_idx.shape[0] if re_idx is not None else R
     llr_dtype = llr_dtype or t.float64
     assert llr_dtype in (t.float32, t.float64)
     nbits = nre * NL * Qm
-    w = words if words is not None else (prbs_words(cinit, nbits) if cinit is not None else None)
+    w = words if words is not None else (None if cinit is None else prbs_words(cinit, nbits))
     llr = t.empty((T, nbits), dtype=llr_dtype, device=y.device)
     outs = {"sym": t.empty((T, nre * NL), dtype=t.complex64, device=y.device) if "sym" in want else None,
             "noise_var": t.empty((T, nre * NL), dtype=llr_dtype, device=y.device) if "noise_var" in want else None,
             "hardbits": t.empty((T, nbits), dtype=t.int8, device=y.device) if "hardbits" in want else None}
-    def ld(x, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
-        return x.stride(0) if T > 1 else row
-    def opt(x):
-        return _lib.ptr(x) if x is not None else None
     code, irc = _lib.ML_ALGO[algo]
-    with t.cuda.device(y.device):
-        _lib.check(_lib.lib().ldpc5g_ml_detect(
-            _lib.ptr(y), ld(y, R * Nr), _lib.ptr(h), ld(h, R * Nr * NL), _lib.ptr(cov),
-            ld(cov, cov.shape[1] * Nr * Nr), _lib.F32 if y.dtype == t.complex64 else _lib.F64,
-            opt(re_idx), R, nre, int(re_per_cov), T, Nr, NL, int(mod), code, irc,
-            opt(w), ld(w, (nbits + 31) // 32) if w is not None else 0, _lib.ptr(llr),
-            _lib.F64 if llr_dtype == t.float64 else _lib.F32, nbits,
-            opt(outs["sym"]), nre * NL, opt(outs["noise_var"]), nre * NL, opt(outs["hardbits"]), nbits,
-            _lib.stream_ptr(y.device)))
+    _lib.call("ldpc5g_ml_detect", y.device, **args, mod=int(mod), algo=code, irc=irc, prbs=w,
+              ldw=0 if w is None else w.stride(0) if T > 1 else (nbits + 31) // 32, llr=llr,
+              llr_dtype=_lib.dtype_id(llr_dtype), ldllr=nbits, sym=outs["sym"], ldsym=nre * NL,
+              noise_var=outs["noise_var"], ldnv=nre * NL, hardbits=outs["hardbits"], ldhb=nbits)
     return (llr, *(outs[k] for k in want)) if want else llr
 
 
@@ -225,7 +203,7 @@ def channel_estimate(h_ls, sym_map, algo, scs, eRB, l_left_ns, l_right_ns, re_di
     else:
         h = t.empty((T, 14 * ND, Nr, Nt), dtype=h_ls.dtype, device=dev)
         cov = t.empty((T, 14 * PRB, Nr, Nr), dtype=h_ls.dtype, device=dev)
-    need = int(_lib.lib().ldpc5g_ce_workspace_bytes(T, S, N, Nr, Nt, D))
+    need = int(_lib.invoke("ldpc5g_ce_workspace_bytes", T=T, S=S, N=N, Nr=Nr, Nt=Nt, D=D))
     if work is None:
         work = t.empty((max(need, 16),), dtype=t.uint8, device=dev)
     assert work.dtype == t.uint8 and work.is_contiguous() and work.device == dev
@@ -236,19 +214,15 @@ def channel_estimate(h_ls, sym_map, algo, scs, eRB, l_left_ns, l_right_ns, re_di
         "to_est": t.empty((T, S), dtype=t.float64, device=dev) if "to_est" in want else None,
         "to_avg": t.empty((T,), dtype=t.float64, device=dev) if "to_avg" in want else None,
         "h_ls_comp": t.empty((T, S, N, Nr, Nt), dtype=h_ls.dtype, device=dev) if "h_ls_comp" in want else None}
-    def ld(x, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
-        return x.stride(0) if T > 1 else row
-    def opt(x):
-        return _lib.ptr(x) if x is not None else None
+    ld = _lib.row_stride
     sym_arr = (_lib.ctypes.c_int32 * max(S, 1))(*sym)
-    with t.cuda.device(dev):
-        _lib.check(_lib.lib().ldpc5g_channel_estimate(
-            _lib.ptr(h_ls), ld(h_ls, S * N * Nr * Nt), _lib.F32 if h_ls.dtype == t.complex64 else _lib.F64,
-            T, S, N, Nr, Nt, D, sym_arr, _lib.CE_ALGO[algo], eK, L_left, L_right, int(num_cdm_groups),
-            1 if to_comp else 0, int(scs), _lib.ptr(h), ld(h, 14 * ND * Nr * Nt), _lib.ptr(cov),
-            ld(cov, 14 * PRB * Nr * Nr), _lib.ptr(work), work.numel(), opt(outs["h_ls_comp"]), S * N * Nr * Nt,
-            opt(outs["h_est"]), opt(outs["noise_power"]), opt(outs["taps"]), opt(outs["to_est"]),
-            opt(outs["to_avg"]), _lib.stream_ptr(dev)))
+    _lib.call("ldpc5g_channel_estimate", dev, h_ls=h_ls, ldhls=ld(h_ls, 0, S * N * Nr * Nt),
+              in_dtype=_lib.dtype_id(h_ls.dtype), T=T, S=S, N=N, Nr=Nr, Nt=Nt, D=D, sym_idx=sym_arr,
+              algo=_lib.CE_ALGO[algo], eK=eK, L_left=L_left, L_right=L_right, num_cdm_groups=int(num_cdm_groups),
+              to_comp=1 if to_comp else 0, scs=int(scs), h=h, ldh=ld(h, 0, 14 * ND * Nr * Nt), cov=cov,
+              ldcov=ld(cov, 0, 14 * PRB * Nr * Nr), work=work, work_bytes=work.numel(),
+              h_ls_comp=outs["h_ls_comp"], ldhc=S * N * Nr * Nt, h_est=outs["h_est"],
+              noise_power=outs["noise_power"], taps=outs["taps"], to_est=outs["to_est"], to_avg=outs["to_avg"])
     return (h, cov, {k: outs[k] for k in want}) if want else (h, cov)
 
 
@@ -265,11 +239,9 @@ def to_compensate(y, to_avg, scs, out=None):
         out = t.empty((T, nsym, RE, Nr), dtype=y.dtype, device=y.device)
     assert out.dtype == y.dtype and out.shape == y.shape and out[0].is_contiguous()
     row = nsym * RE * Nr
-    with t.cuda.device(y.device):
-        _lib.check(_lib.lib().ldpc5g_to_compensate(
-            _lib.ptr(y), y.stride(0) if T > 1 else row, _lib.ptr(out), out.stride(0) if T > 1 else row,
-            _lib.F32 if y.dtype == t.complex64 else _lib.F64, _lib.ptr(to_avg), T, nsym, RE, Nr, int(scs),
-            _lib.stream_ptr(y.device)))
+    _lib.call("ldpc5g_to_compensate", y.device, y=y, ldy=_lib.row_stride(y, 0, row), out=out,
+              ldo=_lib.row_stride(out, 0, row), in_dtype=_lib.dtype_id(y.dtype), to_avg=to_avg, T=T, nsym=nsym,
+              RE=RE, Nr=Nr, scs=int(scs))
     return out
 
 
@@ -285,16 +257,12 @@ def demod_descramble(sym, noise_var, mod, cinit=None, words=None, out=None, llr_
     nv = noise_var if noise_var.dtype == t.float32 and noise_var.is_contiguous() else \
         noise_var.to(t.float32).contiguous()
     assert nv.shape == (T, n)
-    w = words if words is not None else (prbs_words(cinit, n * Qm) if cinit is not None else None)
+    w = words if words is not None else (None if cinit is None else prbs_words(cinit, n * Qm))
     llr = out if out is not None else t.empty((T, n * Qm), dtype=llr_dtype, device=sym.device)
     assert llr.dtype in (t.float32, t.float64) and llr.shape == (T, n * Qm) and llr.stride(1) == 1
-    with t.cuda.device(sym.device):
-        _lib.check(_lib.lib().ldpc5g_demod_descramble(
-            _lib.ptr(sym), _lib.F32 if sym.dtype == t.complex64 else _lib.F64, sym.stride(0),
-            _lib.ptr(nv), nv.stride(0), _lib.ptr(w) if w is not None else None,
-            w.stride(0) if w is not None else 0, T, n, int(mod), _lib.ptr(llr),
-            _lib.F64 if llr.dtype == t.float64 else _lib.F32, llr.stride(0),
-            _lib.stream_ptr(sym.device)))
+    _lib.call("ldpc5g_demod_descramble", sym.device, sym=sym, sym_dtype=_lib.dtype_id(sym.dtype),
+              ldsym=sym.stride(0), noise_var=nv, ldnv=nv.stride(0), prbs=w, ldw=w.stride(0) if w is not None else 0,
+              T=T, nsym=n, mod=int(mod), llr=llr, llr_dtype=_lib.dtype_id(llr.dtype), ldllr=llr.stride(0))
     return llr
 
 
@@ -378,18 +346,10 @@ def slot_data_re_idx_device(pdsch_config, device):
     return t.from_numpy(slot_data_re_idx(pdsch_config)[0]).to(device)
 
 
-def _st(x, d, row):   # the stride of a size-1 dimension is arbitrary in torch (and unused here)
-    return x.stride(d) if x.shape[d] > 1 else row
-
-
-def _optr(x):
-    return _lib.ptr(x) if x is not None else None
-
-
 def _frontend(grid, slots, want, params, entry, seq_args):
     """What slot_frontend and pusch_tp_frontend share.  params(): the configuration's fields after
     the asserts and refusals that come before any GPU work; entry: the library call; seq_args(p, T,
-    S, dev): its arguments between Nr and S and between sym_idx and h_ls (the DMRS sequence's)."""
+    S, dev): the keyword arguments only that entry has (the layers' ports and the DMRS sequence's)."""
     assert want and all(w in ("h_ls", "y") for w in want), f"want {want!r}: a selection of 'h_ls', 'y'"
     p = params()
     t = _lib.require_gpu()
@@ -400,15 +360,13 @@ def _frontend(grid, slots, want, params, entry, seq_args):
     assert slots.shape == (T,) and slots.dtype == t.int32 and slots.is_contiguous() and slots.device == grid.device
     S, N, NL = len(p["symlist"]), 3 * p["rb_size"], p["NL"]
     dev = grid.device
-    first, rest = seq_args(p, T, S, dev)
+    variant = seq_args(p, T, S, dev)
     h_ls = t.empty((T, S, N, Nr, NL), dtype=grid.dtype, device=dev) if "h_ls" in want else None
     y = t.empty((T, 14 * 4 * N, Nr), dtype=grid.dtype, device=dev) if "y" in want else None
     syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
-    with t.cuda.device(dev):
-        _lib.check(getattr(_lib.lib(), entry)(
-            _lib.ptr(grid), _st(grid, 0, Nr * W), _lib.F32 if grid.dtype == t.complex64 else _lib.F64,
-            _lib.ptr(slots), T, W // 14, p["rb_start"], p["rb_size"], Nr, *first, S, syms, *rest,
-            _optr(h_ls), S * N * Nr * NL, _optr(y), 14 * 4 * N * Nr, _lib.stream_ptr(dev)))
+    _lib.call(entry, dev, grid=grid, ldgrid=_lib.row_stride(grid, 0, Nr * W), in_dtype=_lib.dtype_id(grid.dtype),
+              slots=slots, T=T, carrier_re=W // 14, rb_start=p["rb_start"], rb_size=p["rb_size"], Nr=Nr, S=S,
+              sym_idx=syms, h_ls=h_ls, ldh=S * N * Nr * NL, y=y, ldy=14 * 4 * N * Nr, **variant)
     outs = {"h_ls": h_ls, "y": y}
     return tuple(outs[w] for w in want)
 
@@ -424,15 +382,15 @@ def slot_frontend(grid, slots, pdsch_config, want=("h_ls", "y")):
     y (T, 14*12*RBSize, Nr) — the allocation's PRBs of all 14 symbols, interleaved — of grid's dtype."""
     def seq_args(p, T, S, dev):
         ports = (_lib.ctypes.c_int32 * 4)(*[q - 1000 for q in p["ports"]])
-        return (p["NL"], ports), (p["nid"], p["nscid"], p["cdm"])
+        return dict(Nt=p["NL"], ports=ports, nNIDnSCID=p["nid"], nSCID=p["nscid"], num_cdm_groups=p["cdm"])
     return _frontend(grid, slots, want, lambda: _slot_params(pdsch_config), "ldpc5g_slot_rx_frontend", seq_args)
 
 
-def _map(t, sym, slots, p, carrier_prbs, num_ant, precoding, out, re_idx, entry, seq_args):
+def _map(t, sym, slots, p, carrier_prbs, num_ant, precoding, out, re_idx, entry, seq_args, prepare=None):
     """What slot_map and pusch_tp_map share, after their parameter extraction.  re_idx: the
-    device tensor; entry: the library call; seq_args(T, S, dev): its argument between num_ant and
-    precoding, those between sym_idx and grid (the DMRS sequence's), and what becomes of sym on its
-    way into the call."""
+    device tensor; entry: the library call; seq_args(T, S, dev): the keyword arguments only that
+    entry has (the layers and the DMRS sequence's); prepare: what becomes of sym on its way into
+    the call."""
     import numpy as np
     NL, dev, num_ant = p["NL"], sym.device, int(num_ant)
     assert re_idx.dim() == 1 and re_idx.dtype == t.int32 and re_idx.is_contiguous() and re_idx.device == dev
@@ -450,16 +408,15 @@ def _map(t, sym, slots, p, carrier_prbs, num_ant, precoding, out, re_idx, entry,
         w = np.asarray(precoding, np.complex64)
         w = np.ascontiguousarray((w.reshape(-1, 1) if NL == 1 else w)[:num_ant, :NL])
         assert w.shape == (num_ant, NL), f"precoding {w.shape}: (num_ant, NL) = ({num_ant}, {NL}) wanted"
-        pm = w.view(np.float32).ctypes.data_as(_lib.ctypes.c_void_p)
+        pm = w   # (num_ant, NL) complex64 = the ABI's interleaved float pairs
     S = len(p["symlist"])
-    first, rest, prepare = seq_args(T, S, dev)
-    sym = prepare(sym)
+    variant = seq_args(T, S, dev)
+    if prepare is not None:
+        sym = prepare(sym)
     syms = (_lib.ctypes.c_int32 * 4)(*p["symlist"])
-    with t.cuda.device(dev):
-        _lib.check(getattr(_lib.lib(), entry)(
-            _lib.ptr(sym), _st(sym, 0, nre * NL), _lib.ptr(re_idx), nre, _lib.ptr(slots), T, W // 14,
-            p["rb_start"], p["rb_size"], num_ant, first, pm, S, syms, *rest,
-            _lib.ptr(out), _st(out, 0, num_ant * W), _lib.stream_ptr(dev)))
+    _lib.call(entry, dev, sym=sym, ldsym=_lib.row_stride(sym, 0, nre * NL), re_idx=re_idx, nre=nre, slots=slots,
+              T=T, carrier_re=W // 14, rb_start=p["rb_start"], rb_size=p["rb_size"], num_ant=num_ant,
+              precoding=pm, S=S, sym_idx=syms, grid=out, ldgrid=_lib.row_stride(out, 0, num_ant * W), **variant)
     return out
 
 
@@ -480,7 +437,7 @@ def slot_map(sym, slots, pdsch_config, carrier_prbs, num_ant, precoding=None, ou
     if re_idx is None:
         re_idx = slot_data_re_idx_device(pdsch_config, sym.device)
     return _map(t, sym, slots, p, carrier_prbs, num_ant, precoding, out, re_idx, "ldpc5g_slot_map",
-                lambda T, S, dev: (NL, (p["nid"], p["nscid"], p["cdm"]), lambda x: x))
+                lambda T, S, dev: dict(NL=NL, nNIDnSCID=p["nid"], nSCID=p["nscid"], num_cdm_groups=p["cdm"]))
 
 
 # ------------------------------------------------------------------ PUSCH transform precoding
@@ -521,11 +478,9 @@ def transform_precode(x, rb_size, inverse=False, out=None):
     if out is None:
         out = t.empty((T, W), dtype=x.dtype, device=x.device)
     assert out.dtype == x.dtype and out.shape == (T, W) and out.stride(1) == 1 and out.device == x.device
-    with t.cuda.device(x.device):
-        _lib.check(_lib.lib().ldpc5g_transform_precode(
-            _lib.ptr(x), _st(x, 0, W), _lib.ptr(out), _st(out, 0, W),
-            _lib.F32 if x.dtype == t.complex64 else _lib.F64, T, W // M, int(rb_size), 1 if inverse else 0,
-            _lib.stream_ptr(x.device)))
+    _lib.call("ldpc5g_transform_precode", x.device, x=x, ldx=_lib.row_stride(x, 0, W), out=out,
+              ldo=_lib.row_stride(out, 0, W), in_dtype=_lib.dtype_id(x.dtype), T=T, nsym=W // M,
+              rb_size=int(rb_size), inverse=1 if inverse else 0)
     return out
 
 
@@ -556,9 +511,7 @@ def low_papr_seq(u, v, MZC, alpha=0.0, device=None):
     assert v.shape == u.shape and v.dtype == t.int32 and v.is_contiguous() and v.device == u.device
     n = u.shape[0]
     out = t.empty((n, MZC), dtype=t.complex128, device=u.device)
-    with t.cuda.device(u.device):
-        _lib.check(_lib.lib().ldpc5g_low_papr_seq(_lib.ptr(u), _lib.ptr(v), n, float(alpha), MZC, _lib.ptr(out),
-                                                  _lib.stream_ptr(u.device)))
+    _lib.call("ldpc5g_low_papr_seq", u.device, u=u, v=v, n=n, alpha=float(alpha), MZC=MZC, out=out)
     return out
 
 
@@ -608,9 +561,9 @@ def _tp_base_seq(base_seq, T, S, MZC, dev):
 
 
 def _tp_seq_args(p, base_seq, T, S, dev):
-    """(port, (nPuschID, hopping, base_seq)) of the two _tp library calls"""
+    """The keyword arguments only the two _tp library calls have"""
     bs = _tp_base_seq(base_seq, T, S, 6 * p["rb_size"], dev)
-    return p["ports"][0] - 1000, (p["npuschid"], p["hopping"], _optr(bs))
+    return dict(port=p["ports"][0] - 1000, nPuschID=p["npuschid"], hopping=p["hopping"], base_seq=bs)
 
 
 def pusch_tp_frontend(grid, slots, pusch_config, want=("h_ls", "y"), base_seq=None):
@@ -620,11 +573,8 @@ def pusch_tp_frontend(grid, slots, pusch_config, want=("h_ls", "y"), base_seq=No
     base_seq: the DMRS base sequences, (S, 6*RBSize) or (T, S, 6*RBSize) complex128 (host array or
     device tensor), instead of the generated ones; needed for RBSize <= 4.  Returns, in the order of
     `want`, h_ls (T, S, 3*RBSize, Nr, 1) and y (T, 14*12*RBSize, Nr) of grid's dtype."""
-    def seq_args(p, T, S, dev):
-        port, rest = _tp_seq_args(p, base_seq, T, S, dev)
-        return (port,), rest
     return _frontend(grid, slots, want, lambda: _tp_params(pusch_config, base_seq), "ldpc5g_slot_rx_frontend_tp",
-                     seq_args)
+                     lambda p, T, S, dev: _tp_seq_args(p, base_seq, T, S, dev))
 
 
 def pusch_tp_map(sym, slots, pusch_config, carrier_prbs, num_ant, precoding=None, out=None, re_idx=None,
@@ -641,7 +591,8 @@ def pusch_tp_map(sym, slots, pusch_config, carrier_prbs, num_ant, precoding=None
     if re_idx is None:
         re_idx = t.from_numpy(pusch_tp_data_re_idx(pusch_config)[0]).to(sym.device)
     return _map(t, sym, slots, p, carrier_prbs, num_ant, precoding, out, re_idx, "ldpc5g_slot_map_tp",
-                lambda T, S, dev: (*_tp_seq_args(p, base_seq, T, S, dev), lambda x: transform_precode(x, p["rb_size"])))
+                lambda T, S, dev: _tp_seq_args(p, base_seq, T, S, dev),
+                prepare=lambda x: transform_precode(x, p["rb_size"]))
 
 
 # ------------------------------------------------------------------ OFDM low-PHY
@@ -699,11 +650,10 @@ def ofdm_demod(td, scs, carrier_prbs, carrier_frequency_in_mhz=0, out=None):
     if out is None:
         out = t.empty((T, Nr, W), dtype=td.dtype, device=td.device)
     _ofdm_check(t, out, "out", W, td)
-    with t.cuda.device(td.device):
-        _lib.check(_lib.lib().ldpc5g_ofdm_demod(
-            _lib.ptr(td), _st(td, 0, S), _st(td, 1, S), _lib.ptr(out), _st(out, 0, W), _st(out, 1, W),
-            _lib.F32 if td.dtype == t.complex64 else _lib.F64, T, Nr, nfft, W // 14, int(scs), hz,
-            _lib.stream_ptr(td.device)))
+    ld = _lib.row_stride
+    _lib.call("ldpc5g_ofdm_demod", td.device, td=td, ld_td_slot=ld(td, 0, S), ld_td_ant=ld(td, 1, S), grid=out,
+              ld_g_slot=ld(out, 0, W), ld_g_ant=ld(out, 1, W), dtype=_lib.dtype_id(td.dtype), T=T, Nr=Nr, nfft=nfft,
+              carrier_re=W // 14, scs=int(scs), carrier_hz=hz)
     return out
 
 
@@ -728,10 +678,8 @@ def ofdm_mod(grid, scs, carrier_prbs, carrier_frequency_in_mhz=0, dm=None, out=N
     if out is None:
         out = t.empty((T, Na, S), dtype=grid.dtype, device=grid.device)
     _ofdm_check(t, out, "out", S, grid)
-    with t.cuda.device(grid.device):
-        _lib.check(_lib.lib().ldpc5g_ofdm_mod(
-            _lib.ptr(grid), _st(grid, 0, W), _st(grid, 1, W), _lib.ptr(dm) if dm is not None else None,
-            _lib.ptr(out), _st(out, 0, S), _st(out, 1, S),
-            _lib.F32 if grid.dtype == t.complex64 else _lib.F64, T, Na, nfft, W // 14, int(scs), hz,
-            _lib.stream_ptr(grid.device)))
+    ld = _lib.row_stride
+    _lib.call("ldpc5g_ofdm_mod", grid.device, grid=grid, ld_g_slot=ld(grid, 0, W), ld_g_ant=ld(grid, 1, W), dm=dm,
+              td=out, ld_td_slot=ld(out, 0, S), ld_td_ant=ld(out, 1, S), dtype=_lib.dtype_id(grid.dtype), T=T,
+              num_ant=Na, nfft=nfft, carrier_re=W // 14, scs=int(scs), carrier_hz=hz)
     return out

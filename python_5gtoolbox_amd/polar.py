@@ -51,15 +51,10 @@ class Plan:
 
 def plan_blob(K, E, nMax, iIL, CRCLEN=24, padCRC=0, rnti=0):
     """The plan's bytes (numpy uint8); AssertionError with the library's message for refused arguments."""
-    lib = _lib.lib()
-    args = [int(K), int(E), int(nMax), int(iIL), int(CRCLEN), int(padCRC), int(rnti)]
-    n = lib.ldpc5g_polar_plan(*args, None, 0)
-    if n < 0:
-        _lib.check(int(n))
+    args = dict(K=int(K), E=int(E), nMax=int(nMax), iIL=int(iIL), crclen=int(CRCLEN), padCRC=int(padCRC), rnti=int(rnti))
+    n = _lib.call("ldpc5g_polar_plan", **args, plan=None, plan_bytes=0)
     blob = np.zeros(int(n), np.uint8)
-    n2 = lib.ldpc5g_polar_plan(*args, ctypes.c_void_p(blob.ctypes.data), int(n))
-    if n2 < 0:
-        _lib.check(int(n2))
+    _lib.call("ldpc5g_polar_plan", **args, plan=blob, plan_bytes=int(n))
     return blob
 
 
@@ -82,18 +77,16 @@ def _rows(x, width, dtype, name):
 def encode(bits, p):
     t, bits, ld = _rows(bits, p.K, _lib.torch().int8, "bits")
     out = t.empty((bits.shape[0], p.N), dtype=t.int8, device=bits.device)
-    with t.cuda.device(bits.device):
-        _lib.check(_lib.lib().ldpc5g_polar_encode(_lib.ptr(p.dev(bits.device)), p.host, _lib.ptr(bits), ld, _lib.ptr(out),
-                                                  p.N, bits.shape[0], _lib.stream_ptr()))
+    _lib.call("ldpc5g_polar_encode", bits.device, plan_dev=p.dev(bits.device), plan_host=p.host, bits=bits, ldb=ld,
+              out=out, ldo=p.N, B=bits.shape[0])
     return out
 
 
 def rate_match(d, p, iBIL):
     t, d, ld = _rows(d, p.N, _lib.torch().int8, "d")
     out = t.empty((d.shape[0], p.E), dtype=t.int8, device=d.device)
-    with t.cuda.device(d.device):
-        _lib.check(_lib.lib().ldpc5g_polar_rate_match(_lib.ptr(p.dev(d.device)), p.host, _lib.ptr(d), ld, _lib.ptr(out),
-                                                      p.E, d.shape[0], int(iBIL), _lib.stream_ptr()))
+    _lib.call("ldpc5g_polar_rate_match", d.device, plan_dev=p.dev(d.device), plan_host=p.host, d=d, ldi=ld, f=out,
+              ldo=p.E, B=d.shape[0], iBIL=int(iBIL))
     return out
 
 
@@ -102,10 +95,9 @@ def rate_recover(llr, p, iBIL, LLR_limit=20.0, reference_repetition=False):
     them, as nr_polar_raterecover.py:40 does; the default de-interleaves."""
     t, llr, ld = _rows(llr, p.E, _lib.torch().float64, "llr")
     out = t.empty((llr.shape[0], p.N), dtype=t.float64, device=llr.device)
-    with t.cuda.device(llr.device):
-        _lib.check(_lib.lib().ldpc5g_polar_rate_recover(_lib.ptr(p.dev(llr.device)), p.host, _lib.ptr(llr), ld,
-                                                        _lib.ptr(out), p.N, llr.shape[0], int(iBIL), float(LLR_limit),
-                                                        int(bool(reference_repetition)), _lib.stream_ptr()))
+    _lib.call("ldpc5g_polar_rate_recover", llr.device, plan_dev=p.dev(llr.device), plan_host=p.host, llr=llr, ldi=ld,
+              out=out, ldo=p.N, B=llr.shape[0], iBIL=int(iBIL), llr_limit=float(LLR_limit),
+              reference_repetition=int(bool(reference_repetition)))
     return out
 
 
@@ -118,10 +110,8 @@ def decode(llr, p, algo="SCL", L=8):
     ck = t.empty((B, p.K), dtype=t.int8, device=llr.device)
     status = t.empty(B, dtype=t.uint8, device=llr.device)
     pm = t.empty(B, dtype=t.float64, device=llr.device)
-    with t.cuda.device(llr.device):
-        _lib.check(_lib.lib().ldpc5g_polar_decode(_lib.ptr(p.dev(llr.device)), p.host, _lib.ptr(llr), ld, _lib.ptr(ck), p.K,
-                                                  _lib.ptr(status), _lib.ptr(pm), B, ALGOS[algo], int(L),
-                                                  _lib.stream_ptr()))
+    _lib.call("ldpc5g_polar_decode", llr.device, plan_dev=p.dev(llr.device), plan_host=p.host, llr=llr, ldl=ld, ck=ck,
+              ldc=p.K, status=status, pm=pm, B=B, algo=ALGOS[algo], L=int(L))
     return ck, status, pm
 
 

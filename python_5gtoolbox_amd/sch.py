@@ -32,8 +32,8 @@ def sch_config(A, Qm, coderateby1024, NL, rv, TBS_LBRM, G):
     """Transport-block geometry (ldpc5g_sch_config).  TBS_LBRM > 0: DL-SCH limited-buffer Ncb
     (nr_dlsch.py:63-65); TBS_LBRM = 0: UL-SCH Ncb = N (nr_ulsch.py:55-58)."""
     cfg = _lib.SchCfg()
-    _lib.check(_lib.lib().ldpc5g_sch_config(int(A), int(Qm), float(coderateby1024), int(NL),
-                                            int(rv), int(TBS_LBRM), int(G), _lib.ctypes.byref(cfg)))
+    _lib.call("ldpc5g_sch_config", A=int(A), Qm=int(Qm), coderateby1024=float(coderateby1024), NL=int(NL),
+              rv=int(rv), TBS_LBRM=int(TBS_LBRM), G=int(G), cfg=_lib.ctypes.byref(cfg))
     return cfg
 
 
@@ -70,10 +70,8 @@ def crc_rows(bits, poly, nbits=None):
     n = bits.shape[1] if nbits is None else int(nbits)
     R = bits.shape[0]
     rem = t.empty((max(R, 1),), dtype=t.int32, device=bits.device)
-    with t.cuda.device(bits.device):
-        _lib.check(_lib.lib().ldpc5g_crc(_lib.ptr(bits), bits.stride(0), n, R,
-                                         _lib.CRC_IDS[poly.upper()], _lib.ptr(rem),
-                                         _lib.stream_ptr(bits.device)))
+    _lib.call("ldpc5g_crc", bits.device, bits=bits, ld=bits.stride(0), nbits=n, rows=R,
+              poly=_lib.CRC_IDS[poly.upper()], rem=rem)
     return rem[:R].to(t.int64) & 0xFFFFFFFF
 
 
@@ -115,11 +113,6 @@ class SchWorkspace:
         return self.rx_llr[dtype]
 
 
-def _dtype_id(t, dt):
-    assert dt in (t.float32, t.float64), "LLRs must be float32 or float64"
-    return _lib.F32 if dt == t.float32 else _lib.F64
-
-
 def sch_segment_batch(trblk, cfg, ws=None):
     """TB CRC + codeblock segmentation + CRC24B of T transport blocks (ldpc5g_sch_segment):
     returns (ck (T*C, K) int8 with -1 fillers, tb_crc (T,) int32)."""
@@ -128,10 +121,8 @@ def sch_segment_batch(trblk, cfg, ws=None):
     T = trblk.shape[0]
     assert trblk.shape[1] >= cfg.A
     ws = ws or SchWorkspace(cfg, T, trblk.device)
-    with t.cuda.device(trblk.device):
-        _lib.check(_lib.lib().ldpc5g_sch_segment(
-            _lib.ptr(trblk), trblk.stride(0), _lib.ctypes.byref(cfg), T, _lib.ptr(ws.ck),
-            _lib.ptr(ws.tb_crc), _lib.stream_ptr(trblk.device)))
+    _lib.call("ldpc5g_sch_segment", trblk.device, trblk=trblk, lda=trblk.stride(0),
+              cfg=_lib.ctypes.byref(cfg), T=T, ck=ws.ck, tb_crc=ws.tb_crc)
     return ws.ck, ws.tb_crc
 
 
@@ -141,10 +132,8 @@ def sch_ratematch_batch(ck, cfg, T, ws=None):
     t = _lib.require_gpu()
     assert ck.dim() == 2 and ck.dtype == t.int8 and ck.shape == (T * cfg.C, cfg.K) and ck.is_contiguous()
     ws = ws or SchWorkspace(cfg, T, ck.device)
-    with t.cuda.device(ck.device):
-        _lib.check(_lib.lib().ldpc5g_sch_ratematch(
-            _lib.ptr(ck), _lib.ctypes.byref(cfg), T, _lib.ptr(ws.dn), _lib.ptr(ws.g),
-            ws.g.stride(0), _lib.stream_ptr(ck.device)))
+    _lib.call("ldpc5g_sch_ratematch", ck.device, ck=ck, cfg=_lib.ctypes.byref(cfg), T=T, dn=ws.dn,
+              g=ws.g, ldg=ws.g.stride(0))
     return ws.g[:, :cfg.E_total]
 
 
@@ -156,11 +145,8 @@ def sch_encode_batch(trblk, cfg, ws=None):
     T = trblk.shape[0]
     assert trblk.shape[1] >= cfg.A
     ws = ws or SchWorkspace(cfg, T, trblk.device)
-    with t.cuda.device(trblk.device):
-        _lib.check(_lib.lib().ldpc5g_sch_encode(
-            _lib.ptr(trblk), trblk.stride(0), _lib.ptr(ws.g), ws.g.stride(0),
-            _lib.ctypes.byref(cfg), T, _lib.ptr(ws.ck), _lib.ptr(ws.dn), _lib.ptr(ws.tb_crc),
-            _lib.stream_ptr(trblk.device)))
+    _lib.call("ldpc5g_sch_encode", trblk.device, trblk=trblk, lda=trblk.stride(0), g=ws.g,
+              ldg=ws.g.stride(0), cfg=_lib.ctypes.byref(cfg), T=T, ck=ws.ck, dn=ws.dn, tb_crc=ws.tb_crc)
     return ws.g[:, :cfg.E_total]
 
 
@@ -176,12 +162,15 @@ def sch_raterecover_batch(llr, cfg, harq_in=None, dn_dtype=None, ws=None):
     out = ws.dn_buf(dn_dtype, cfg)
     if harq_in is not None:
         assert harq_in.dtype == dn_dtype and harq_in.shape == out.shape and harq_in.is_contiguous()
-    with t.cuda.device(llr.device):
-        _lib.check(_lib.lib().ldpc5g_sch_raterecover(
-            _lib.ptr(llr), _dtype_id(t, llr.dtype), llr.stride(0), _lib.ctypes.byref(cfg), T,
-            _lib.ptr(harq_in) if harq_in is not None else None, _lib.ptr(out),
-            _dtype_id(t, dn_dtype), _lib.stream_ptr(llr.device)))
+    _lib.call("ldpc5g_sch_raterecover", llr.device, llr=llr, llr_dtype=_lib.dtype_id(llr.dtype, llr=True),
+              ldg=llr.stride(0), cfg=_lib.ctypes.byref(cfg), T=T, harq_in=harq_in, llr_dn=out,
+              dn_dtype=_lib.dtype_id(dn_dtype, llr=True))
     return out
+
+
+def _tb_outputs(ws):
+    """The TB reassembly outputs of ldpc5g_sch_tb_check and of the decode chains that end in it."""
+    return dict(tbblk=ws.tbblk, ldb=ws.tbblk.stride(0), cb_crc_ok=ws.cb_ok, tb_rem=ws.tb_rem, tb_ok=ws.tb_ok)
 
 
 def sch_tb_check_batch(ck, cfg, T, ws=None):
@@ -189,11 +178,8 @@ def sch_tb_check_batch(ck, cfg, T, ws=None):
     t = _lib.require_gpu()
     assert ck.dim() == 2 and ck.dtype == t.int8 and ck.stride(1) == 1 and ck.shape[0] == T * cfg.C
     ws = ws or SchWorkspace(cfg, T, ck.device)
-    with t.cuda.device(ck.device):
-        _lib.check(_lib.lib().ldpc5g_sch_tb_check(
-            _lib.ptr(ck), ck.stride(0), _lib.ctypes.byref(cfg), T, _lib.ptr(ws.tbblk),
-            ws.tbblk.stride(0), _lib.ptr(ws.cb_ok), _lib.ptr(ws.tb_rem), _lib.ptr(ws.tb_ok),
-            _lib.stream_ptr(ck.device)))
+    _lib.call("ldpc5g_sch_tb_check", ck.device, ck=ck, ldc=ck.stride(0), cfg=_lib.ctypes.byref(cfg), T=T,
+              **_tb_outputs(ws))
     return ws.tb_ok, ws.tbblk, ws.cb_ok, ws.tb_rem
 
 
@@ -234,14 +220,10 @@ def sch_decode_batch(llr, cfg, L, algo="min-sum", alpha=1.0, beta=0.0, schedule=
             assert harq_in.dtype == dn_dtype and harq_in.shape == out.shape and harq_in.is_contiguous()
         assert llr.dim() == 2 and llr.stride(1) == 1 and llr.shape[1] >= cfg.E_total
         sched = {"flooding": _lib.FLOODING, "layered": _lib.LAYERED}[schedule]
-        with t.cuda.device(llr.device):
-            _lib.check(_lib.lib().ldpc5g_sch_decode(
-                _lib.ptr(llr), _dtype_id(t, llr.dtype), llr.stride(0), _lib.ctypes.byref(cfg), T,
-                _lib.ptr(harq_in) if harq_in is not None else None, _lib.ptr(out),
-                _dtype_id(t, dn_dtype), _lib.ptr(ws.dec_ck), _lib.ptr(ws.status),
-                _lib.ptr(ws.iters), int(L), float(alpha), float(beta), sched, _lib.ptr(ws.tbblk),
-                ws.tbblk.stride(0), _lib.ptr(ws.cb_ok), _lib.ptr(ws.tb_rem), _lib.ptr(ws.tb_ok),
-                _lib.stream_ptr(llr.device)))
+        _lib.call("ldpc5g_sch_decode", llr.device, llr=llr, llr_dtype=_lib.dtype_id(llr.dtype, llr=True),
+                  ldg=llr.stride(0), cfg=_lib.ctypes.byref(cfg), T=T, harq_in=harq_in, llr_dn=out,
+                  dn_dtype=_lib.dtype_id(dn_dtype, llr=True), ck=ws.dec_ck, status=ws.status, iters=ws.iters,
+                  L=int(L), alpha=float(alpha), beta=float(beta), schedule=sched, **_tb_outputs(ws))
         llr_dn = out
     else:
         from .nr_ldpc_decode import nr_decode_ldpc_batch
@@ -256,8 +238,9 @@ def sch_decode_batch(llr, cfg, L, algo="min-sum", alpha=1.0, beta=0.0, schedule=
 
 # ------------------------------------------------------------ fused receive front end
 def _rx_args(sym, noise_var, mod, cfg, cinit, words, harq_in, dn_dtype, ws):
-    """Checked inputs of the fused front end -> (T, workspace, the 15 C arguments before `stream`,
-    llr_dn, the temporaries the launch reads: kept alive by the caller until it is queued)."""
+    """Checked inputs of the fused front end -> (T, workspace, the keyword arguments that
+    ldpc5g_sch_demod_raterecover and ldpc5g_sch_rx_decode share, llr_dn).  The keywords hold the
+    temporaries the launch reads (nv, w): the caller keeps them until the call returns."""
     from . import phy
     t = _lib.require_gpu()
     assert sym.dim() == 2 and sym.dtype in (t.complex64, t.complex128) and sym.stride(1) == 1
@@ -268,25 +251,23 @@ def _rx_args(sym, noise_var, mod, cfg, cinit, words, harq_in, dn_dtype, ws):
         noise_var.to(t.float32).contiguous()
     assert nv.dim() == 2 and nv.shape[0] == T and nv.shape[1] >= nsym
     w = words if words is not None else \
-        (phy.prbs_words(cinit, cfg.E_total) if cinit is not None else None)
+        (None if cinit is None else phy.prbs_words(cinit, cfg.E_total))
     if w is not None:
         assert w.dim() == 2 and w.shape[0] == T and w.stride(1) == 1 and w.shape[1] * 32 >= cfg.E_total
     ws = ws or SchWorkspace(cfg, T, sym.device)
     out = ws.dn_buf(dn_dtype, cfg)
     if harq_in is not None:
         assert harq_in.dtype == dn_dtype and harq_in.shape == out.shape and harq_in.is_contiguous()
-    sdt = _lib.F32 if sym.dtype == t.complex64 else _lib.F64
-    need = _lib.lib().ldpc5g_sch_rx_scratch_elems(_lib.ctypes.byref(cfg), int(mod), sdt)
-    _lib.check(int(min(need, 0)))
+    sdt = _lib.dtype_id(sym.dtype)
+    need = _lib.call("ldpc5g_sch_rx_scratch_elems", cfg=_lib.ctypes.byref(cfg), mod=int(mod), sym_dtype=sdt)
     scr = None
     if need:   # a codeblock too large for the LDS stage: the two kernels through this scratch
         scr = ws.rx_scratch(t.float64 if int(mod) == 1 and sdt == _lib.F64 else t.float32, cfg)
-    args = (_lib.ptr(sym), sdt, sym.stride(0), _lib.ptr(nv), nv.stride(0),
-            _lib.ptr(w) if w is not None else None, w.stride(0) if w is not None else 0, int(mod),
-            _lib.ctypes.byref(cfg), T, _lib.ptr(harq_in) if harq_in is not None else None,
-            _lib.ptr(out), _dtype_id(t, dn_dtype), _lib.ptr(scr) if scr is not None else None,
-            scr.stride(0) if scr is not None else 0)
-    return T, ws, args, out, (nv, w)
+    args = dict(sym=sym, sym_dtype=sdt, ldsym=sym.stride(0), noise_var=nv, ldnv=nv.stride(0), prbs=w,
+                ldw=w.stride(0) if w is not None else 0, mod=int(mod), cfg=_lib.ctypes.byref(cfg), T=T,
+                harq_in=harq_in, llr_dn=out, dn_dtype=_lib.dtype_id(dn_dtype, llr=True), llr_ws=scr,
+                ldws=scr.stride(0) if scr is not None else 0)
+    return T, ws, args, out
 
 
 def sch_demod_raterecover_batch(sym, noise_var, mod, cfg, cinit=None, words=None, harq_in=None,
@@ -299,9 +280,8 @@ def sch_demod_raterecover_batch(sym, noise_var, mod, cfg, cinit=None, words=None
     sch_raterecover_batch(phy.demod_descramble(...)), without the LLRs' trip through memory."""
     t = _lib.require_gpu()
     dn_dtype = dn_dtype or (t.float64 if sym.dtype == t.complex128 else t.float32)
-    T, ws, args, out, keep = _rx_args(sym, noise_var, mod, cfg, cinit, words, harq_in, dn_dtype, ws)
-    with t.cuda.device(sym.device):
-        _lib.check(_lib.lib().ldpc5g_sch_demod_raterecover(*args, _lib.stream_ptr(sym.device)))
+    T, ws, args, out = _rx_args(sym, noise_var, mod, cfg, cinit, words, harq_in, dn_dtype, ws)
+    _lib.call("ldpc5g_sch_demod_raterecover", sym.device, **args)
     return out
 
 
@@ -329,14 +309,10 @@ def sch_rx_batch(sym, noise_var, mod, cfg, L, algo="min-sum", alpha=1.0, beta=0.
                                    llr_dtype=t.float64 if f64 else None)
         return sch_decode_batch(llr, cfg, L, algo, alpha, beta, schedule, harq_in, dn_dtype, ws)
     if algo == "min-sum" and not sparse:
-        T, ws, args, llr_dn, keep = _rx_args(sym, noise_var, mod, cfg, cinit, words, harq_in, dn_dtype, ws)
+        T, ws, args, llr_dn = _rx_args(sym, noise_var, mod, cfg, cinit, words, harq_in, dn_dtype, ws)
         sched = {"flooding": _lib.FLOODING, "layered": _lib.LAYERED}[schedule]
-        with t.cuda.device(sym.device):
-            _lib.check(_lib.lib().ldpc5g_sch_rx_decode(
-                *args, _lib.ptr(ws.dec_ck), _lib.ptr(ws.status), _lib.ptr(ws.iters), int(L),
-                float(alpha), float(beta), sched, _lib.ptr(ws.tbblk), ws.tbblk.stride(0),
-                _lib.ptr(ws.cb_ok), _lib.ptr(ws.tb_rem), _lib.ptr(ws.tb_ok),
-                _lib.stream_ptr(sym.device)))
+        _lib.call("ldpc5g_sch_rx_decode", sym.device, **args, ck=ws.dec_ck, status=ws.status, iters=ws.iters,
+                  L=int(L), alpha=float(alpha), beta=float(beta), schedule=sched, **_tb_outputs(ws))
     else:
         T = sym.shape[0]
         ws = ws or SchWorkspace(cfg, T, sym.device)
@@ -585,7 +561,7 @@ def multi_layout(cfgs):
     T = len(cfgs)
     arr = (_lib.SchCfg * max(T, 1))(*cfgs)
     sizes = (_lib.ctypes.c_int64 * 7)()
-    _lib.check(_lib.lib().ldpc5g_sch_multi_sizes(arr, T, sizes))
+    _lib.call("ldpc5g_sch_multi_sizes", cfgs=arr, T=T, sizes=sizes)
     rows, cb, dn, dck = [], 0, 0, 0
     for c in cfgs:
         nf = (68 if c.bgn == 1 else 52) * c.Zc
@@ -609,10 +585,8 @@ def sch_encode_multi(trblk, cfgs):
     ck = t.empty((max(lay["ck"], 1),), dtype=t.int8, device=dev)
     dn = t.empty((max(lay["dn"], 1),), dtype=t.int8, device=dev)
     crc = t.empty((max(T, 1),), dtype=t.int32, device=dev)
-    with t.cuda.device(dev):
-        _lib.check(_lib.lib().ldpc5g_sch_encode_multi(
-            _lib.ptr(trblk), trblk.stride(0), _lib.ptr(g), g.stride(0), lay["arr"], T,
-            _lib.ptr(ck), _lib.ptr(dn), _lib.ptr(crc), _lib.stream_ptr(dev)))
+    _lib.call("ldpc5g_sch_encode_multi", dev, trblk=trblk, lda=trblk.stride(0), g=g, ldg=g.stride(0),
+              cfgs=lay["arr"], T=T, ck=ck, dn=dn, tb_crc=crc)
     return g
 
 
@@ -631,11 +605,9 @@ def sch_raterecover_multi(llr, cfgs, harq_in=None, dn_dtype=None, out=None, lay=
     assert out.dtype == dn_dtype and out.numel() >= lay["dn"] and out.is_contiguous()
     if harq_in is not None:
         assert harq_in.dtype == dn_dtype and harq_in.numel() >= lay["dn"] and harq_in.is_contiguous()
-    with t.cuda.device(llr.device):
-        _lib.check(_lib.lib().ldpc5g_sch_raterecover_multi(
-            _lib.ptr(llr), _dtype_id(t, llr.dtype), llr.stride(0), lay["arr"], T,
-            _lib.ptr(harq_in) if harq_in is not None else None, _lib.ptr(out), _dtype_id(t, dn_dtype),
-            _lib.stream_ptr(llr.device)))
+    _lib.call("ldpc5g_sch_raterecover_multi", llr.device, llr=llr, llr_dtype=_lib.dtype_id(llr.dtype, llr=True),
+              ldg=llr.stride(0), cfgs=lay["arr"], T=T, harq_in=harq_in, llr_dn=out,
+              dn_dtype=_lib.dtype_id(dn_dtype, llr=True))
     return out
 
 
@@ -646,26 +618,21 @@ class SchRaterecoverPlan:
 
     def __init__(self, cfgs, device):
         t = _lib.require_gpu()
-        lib = _lib.lib()
         self.lay = multi_layout(cfgs)
         self.T = len(cfgs)
-        n = lib.ldpc5g_sch_multi_plan(self.lay["arr"], self.T, None, 0)
-        _lib.check(int(min(n, 0)))
+        n = _lib.call("ldpc5g_sch_multi_plan", cfgs=self.lay["arr"], T=self.T, plan=None, plan_bytes=0)
         self.host = t.empty((max(n, 1),), dtype=t.uint8, pin_memory=True)
-        _lib.check(int(min(lib.ldpc5g_sch_multi_plan(self.lay["arr"], self.T, _lib.ptr(self.host), n), 0)))
+        _lib.call("ldpc5g_sch_multi_plan", cfgs=self.lay["arr"], T=self.T, plan=self.host, plan_bytes=n)
         self.dev = self.host.to(device, non_blocking=True)
 
     def __call__(self, llr, out, harq_in=None):
-        t = _lib.torch()
         assert llr.dim() == 2 and llr.shape[0] == self.T and llr.stride(1) == 1
         assert llr.shape[1] >= self.lay["max_E"] and out.is_contiguous() and out.numel() >= self.lay["dn"]
         if harq_in is not None:
             assert harq_in.dtype == out.dtype and harq_in.numel() >= self.lay["dn"] and harq_in.is_contiguous()
-        with t.cuda.device(llr.device):
-            _lib.check(_lib.lib().ldpc5g_sch_raterecover_multi_plan(
-                _lib.ptr(self.dev), _lib.ptr(self.host), _lib.ptr(llr), _dtype_id(t, llr.dtype),
-                llr.stride(0), _lib.ptr(harq_in) if harq_in is not None else None, _lib.ptr(out),
-                _dtype_id(t, out.dtype), _lib.stream_ptr(llr.device)))
+        _lib.call("ldpc5g_sch_raterecover_multi_plan", llr.device, plan_dev=self.dev, plan_host=self.host, llr=llr,
+                  llr_dtype=_lib.dtype_id(llr.dtype, llr=True), ldg=llr.stride(0), harq_in=harq_in, llr_dn=out,
+                  dn_dtype=_lib.dtype_id(out.dtype, llr=True))
         return out
 
 
@@ -695,11 +662,9 @@ def sch_decode_multi(llr, cfgs, L, alpha=1.0, beta=0.0, schedule="flooding", har
     tb_rem = t.empty((max(T, 1),), dtype=t.int32, device=dev)
     tb_ok = t.empty((max(T, 1),), dtype=t.uint8, device=dev)
     sched = {"flooding": _lib.FLOODING, "layered": _lib.LAYERED}[schedule]
-    with t.cuda.device(dev):
-        _lib.check(_lib.lib().ldpc5g_sch_decode_multi(
-            _lib.ptr(llr), _dtype_id(t, llr.dtype), llr.stride(0), lay["arr"], T,
-            _lib.ptr(harq_in) if harq_in is not None else None, _lib.ptr(llr_dn),
-            _dtype_id(t, dn_dtype), _lib.ptr(ck), _lib.ptr(status), _lib.ptr(iters), int(L),
-            float(alpha), float(beta), sched, _lib.ptr(tbblk), tbblk.stride(0), _lib.ptr(cb_ok),
-            _lib.ptr(tb_rem), _lib.ptr(tb_ok), _lib.stream_ptr(dev)))
+    _lib.call("ldpc5g_sch_decode_multi", dev, llr=llr, llr_dtype=_lib.dtype_id(llr.dtype, llr=True),
+              ldg=llr.stride(0), cfgs=lay["arr"], T=T, harq_in=harq_in, llr_dn=llr_dn,
+              dn_dtype=_lib.dtype_id(dn_dtype, llr=True), ck=ck, status=status, iters=iters, L=int(L),
+              alpha=float(alpha), beta=float(beta), schedule=sched, tbblk=tbblk, ldb=tbblk.stride(0),
+              cb_crc_ok=cb_ok, tb_rem=tb_rem, tb_ok=tb_ok)
     return SchMultiResult(tb_ok[:T], tbblk, llr_dn, ck, status, iters, cb_ok, tb_rem, lay["rows"])

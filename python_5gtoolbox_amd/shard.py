@@ -41,6 +41,11 @@ def record_bytes(nbits, status=True, iters=True):
     return (nbits + 7) // 8 + (1 if status else 0) + (4 if iters else 0)
 
 
+def _from(x, r0):
+    """Rows r0.. of an optional tensor: the view lives until the call that reads it returns."""
+    return None if x is None else x[r0:]
+
+
 def pack_records(bits, nbits, status=None, iters=None, out=None):
     """bits (R, >= nbits) int8 device tensor (+ status (R,) uint8, iters (R,) int32) -> records
     (R, record_bytes) uint8 on the same device (`out` may have more rows: only R are written)."""
@@ -50,16 +55,12 @@ def pack_records(bits, nbits, status=None, iters=None, out=None):
     rec = out if out is not None else t.empty((R, rb), dtype=t.uint8, device=bits.device)
     assert rec.dtype == t.uint8 and rec.shape[0] >= R and rec.shape[1] >= rb and rec.stride(1) == 1
     assert bits.dtype == t.int8 and bits.stride(1) == 1 and bits.shape[1] >= nbits
-    with t.cuda.device(bits.device):
-        for r0 in range(0, max(R, 1), 65535):   # grid.y limit
-            n = min(65535, R - r0)
-            if n <= 0:
-                break
-            _lib.check(_lib.lib().ldpc5g_pack_records(
-                _lib.ptr(bits[r0:]), bits.stride(0), n, int(nbits),
-                _lib.ptr(status[r0:]) if status is not None else None,
-                _lib.ptr(iters[r0:]) if iters is not None else None,
-                _lib.ptr(rec[r0:]), rec.stride(0), _lib.stream_ptr(bits.device)))
+    for r0 in range(0, max(R, 1), 65535):   # grid.y limit
+        n = min(65535, R - r0)
+        if n <= 0:
+            break
+        _lib.call("ldpc5g_pack_records", bits.device, bits=bits[r0:], ldb=bits.stride(0), R=n, nbits=int(nbits),
+                  status=_from(status, r0), iters=_from(iters, r0), rec=rec[r0:], ldr=rec.stride(0))
     return rec
 
 
@@ -70,18 +71,13 @@ def unpack_records(rec, R, nbits, bits=None, status=None, iters=None):
     fs = (status if status is not None else iters).stride(0) if (status is not None or iters is not None) else 1
     assert iters is None or status is None or iters.stride(0) == status.stride(0)
     assert bits is None or (bits.dtype == t.int8 and bits.stride(1) == 1)
-    with t.cuda.device(rec.device):
-        for r0 in range(0, max(R, 1), 65535):
-            n = min(65535, R - r0)
-            if n <= 0:
-                break
-            _lib.check(_lib.lib().ldpc5g_unpack_records(
-                _lib.ptr(rec[r0:]), rec.stride(0), n, int(nbits),
-                _lib.ptr(bits[r0:]) if bits is not None else None,
-                bits.stride(0) if bits is not None else 0,
-                _lib.ptr(status[r0:]) if status is not None else None,
-                _lib.ptr(iters[r0:]) if iters is not None else None, fs,
-                _lib.stream_ptr(rec.device)))
+    for r0 in range(0, max(R, 1), 65535):
+        n = min(65535, R - r0)
+        if n <= 0:
+            break
+        _lib.call("ldpc5g_unpack_records", rec.device, rec=rec[r0:], ldr=rec.stride(0), R=n, nbits=int(nbits),
+                  bits=_from(bits, r0), ldb=bits.stride(0) if bits is not None else 0, status=_from(status, r0),
+                  iters=_from(iters, r0), fstride=fs)
 
 
 def gather_record_blocks(torch, dist, rec, counts, rank, world, dst=0, group=None):
@@ -94,7 +90,7 @@ def gather_record_blocks(torch, dist, rec, counts, rank, world, dst=0, group=Non
     assert 0 <= dst < world
     buf = torch.empty((world,) + tuple(rec.shape), dtype=rec.dtype, device=rec.device) \
         if rank == dst else None
-    dist.gather(rec, gather_list=list(buf.unbind(0)) if buf is not None else None,
+    dist.gather(rec, gather_list=None if buf is None else list(buf.unbind(0)),
                 group=group, group_dst=dst)
     return buf
 

@@ -46,11 +46,11 @@ def rm_info(pusch_config, dmrs_symlist, ULSCH_size, Qm, coderateby1024, Gtotal):
     oack, ocsi1, ocsi2 = _payloads(c)
     d = _i32(dmrs_symlist)
     out = np.zeros(9, np.int64)
-    _lib.check(_lib.lib().ldpc5g_uci_rm_info(
-        int(c["ResAlloType1"]["RBSize"]), int(c["StartSymbolIndex"]), int(c["NrOfSymbols"]), ctypes.c_void_p(d.ctypes.data),
-        d.size, int(c["num_of_layers"]), int(Qm), float(coderateby1024), int(ULSCH_size), int(c["EnableULSCH"]), oack, ocsi1,
-        ocsi2, int(c["I_HARQ_ACK_offset"]), int(c["I_CSI1offset"]), int(c["I_CSI2offset"]), float(c["UCIScaling"]),
-        int(Gtotal), ctypes.c_void_p(out.ctypes.data)))
+    _lib.call("ldpc5g_uci_rm_info", RBSize=int(c["ResAlloType1"]["RBSize"]), StartSymbolIndex=int(c["StartSymbolIndex"]),
+              NrOfSymbols=int(c["NrOfSymbols"]), dmrs_symlist=d, num_dmrs=d.size, NL=int(c["num_of_layers"]), Qm=int(Qm),
+              coderateby1024=float(coderateby1024), ULSCH_size=int(ULSCH_size), EnableULSCH=int(c["EnableULSCH"]), OACK=oack,
+              OCSI1=ocsi1, OCSI2=ocsi2, I_HARQ_ACK_offset=int(c["I_HARQ_ACK_offset"]), I_CSI1offset=int(c["I_CSI1offset"]),
+              I_CSI2offset=int(c["I_CSI2offset"]), UCIScaling=float(c["UCIScaling"]), Gtotal=int(Gtotal), out=out)
     return {k: int(v) for k, v in zip(RM_KEYS, out)}
 
 
@@ -97,18 +97,15 @@ class Plan:
 def plan_blob(RBSize, StartSymbolIndex, NrOfSymbols, dmrs_symlist, NumCDMGroupsWithoutData, NL, Qm, OACK, OCSI1, OCSI2,
               EnableULSCH, Euci_ack, Euci_CSI1, Euci_CSI2, Euci_ackrvd, G_ULSCH, Gtotal, frequency_hopping=0):
     """The plan's bytes (numpy uint8); AssertionError with the library's message for refused arguments."""
-    lib = _lib.lib()
     d = _i32(dmrs_symlist)
-    args = [int(RBSize), int(StartSymbolIndex), int(NrOfSymbols), ctypes.c_void_p(d.ctypes.data), d.size,
-            int(NumCDMGroupsWithoutData), int(NL), int(Qm), int(OACK), int(OCSI1), int(OCSI2), int(EnableULSCH),
-            int(frequency_hopping), int(Euci_ack), int(Euci_CSI1), int(Euci_CSI2), int(Euci_ackrvd), int(G_ULSCH), int(Gtotal)]
-    n = lib.ldpc5g_uci_map_plan(*args, None, 0)
-    if n < 0:
-        _lib.check(int(n))
+    args = dict(RBSize=int(RBSize), StartSymbolIndex=int(StartSymbolIndex), NrOfSymbols=int(NrOfSymbols), dmrs_symlist=d,
+                num_dmrs=d.size, NumCDMGroupsWithoutData=int(NumCDMGroupsWithoutData), NL=int(NL), Qm=int(Qm), OACK=int(OACK),
+                OCSI1=int(OCSI1), OCSI2=int(OCSI2), EnableULSCH=int(EnableULSCH), frequency_hopping=int(frequency_hopping),
+                Euci_ack=int(Euci_ack), Euci_CSI1=int(Euci_CSI1), Euci_CSI2=int(Euci_CSI2), Euci_ackrvd=int(Euci_ackrvd),
+                G_ULSCH=int(G_ULSCH), Gtotal=int(Gtotal))
+    n = _lib.call("ldpc5g_uci_map_plan", **args, plan=None, plan_bytes=0)
     blob = np.zeros(int(n), np.uint8)
-    n2 = lib.ldpc5g_uci_map_plan(*args, ctypes.c_void_p(blob.ctypes.data), int(n))
-    if n2 < 0:
-        _lib.check(int(n2))
+    _lib.call("ldpc5g_uci_map_plan", **args, plan=blob, plan_bytes=int(n))
     return blob
 
 
@@ -149,10 +146,6 @@ def _rows(x, width, dtypes, name):
     return t, x, (x.stride(0) if x.shape[0] > 1 else max(width, x.shape[1]))
 
 
-def _dt(t, dtype):
-    return _lib.F32 if dtype == t.float32 else _lib.F64
-
-
 # ---------------------------------------------------------------------------- small-block + polar codec
 def sb_N(K, Qm):
     return Qm if K == 1 else 3 * Qm if K == 2 else 32
@@ -162,9 +155,8 @@ def smallblock_encode(bits, E, Qm):
     t, bits, ld = _rows(bits, 1, (_lib.torch().int8,), "bits")
     T, K = bits.shape
     out = t.empty((T, int(E)), dtype=t.int8, device=bits.device)
-    with t.cuda.device(bits.device):
-        _lib.check(_lib.lib().ldpc5g_smallblock_encode(_lib.ptr(bits), ld, K, int(Qm), _lib.ptr(out), int(E), int(E), T,
-                                                       _lib.stream_ptr()))
+    _lib.call("ldpc5g_smallblock_encode", bits.device, bits=bits, ldb=ld, K=K, Qm=int(Qm), out=out, ldo=int(E), E=int(E),
+              T=T)
     return out
 
 
@@ -173,9 +165,8 @@ def smallblock_decode(llr, K, Qm):
     t, llr, ld = _rows(llr, 1, (t.float32, t.float64), "llr")
     T, E = llr.shape
     out = t.empty((T, int(K)), dtype=t.int8, device=llr.device)
-    with t.cuda.device(llr.device):
-        _lib.check(_lib.lib().ldpc5g_smallblock_decode(_lib.ptr(llr), _dt(t, llr.dtype), ld, E, int(K), int(Qm), _lib.ptr(out),
-                                                       int(K), T, _lib.stream_ptr()))
+    _lib.call("ldpc5g_smallblock_decode", llr.device, llr=llr, dtype=_lib.dtype_id(llr.dtype), ldl=ld, E=E, K=int(K),
+              Qm=int(Qm), out=out, ldo=int(K), T=T)
     return out
 
 
@@ -237,23 +228,19 @@ def mux(p, g_ulsch=None, g_ack=None, g_csi1=None, g_csi2=None):
     """data_control_multiplex (nr_pusch_datactrl_multiplex.py:7-267): the coded streams [T, len] int8
     (None for a stream the plan does not hold) -> g_seq [T, Gtotal] int8."""
     t = _lib.require_gpu()
-    ins, T, dev = [], None, None
+    ins, T, dev = {}, None, None
     for n, x in zip(STREAMS, (g_ulsch, g_ack, g_csi1, g_csi2)):
         if p.lens[n] == 0:
-            ins.append((None, 0))
+            ins["g_" + n], ins["ld_" + n] = None, 0
             continue
         assert x is not None, f"g_{n}: the plan holds {p.lens[n]} bits of it"
         _, x, ld = _rows(x, p.lens[n], (t.int8,), "g_" + n)
         assert T in (None, x.shape[0]), "the streams must have the same number of rows"
         T, dev = x.shape[0], x.device
-        ins.append((x, ld))
+        ins["g_" + n], ins["ld_" + n] = x, ld
     assert T is not None
     g = t.empty((T, p.Gtotal), dtype=t.int8, device=dev)
-    args = []
-    for x, ld in ins:
-        args += [_lib.ptr(x) if x is not None else None, ld]
-    with t.cuda.device(dev):
-        _lib.check(_lib.lib().ldpc5g_uci_mux(_lib.ptr(p.dev(dev)), p.host, *args, _lib.ptr(g), p.Gtotal, T, _lib.stream_ptr()))
+    _lib.call("ldpc5g_uci_mux", dev, plan_dev=p.dev(dev), plan_host=p.host, **ins, g_seq=g, ldg=p.Gtotal, T=T)
     return g
 
 
@@ -267,18 +254,16 @@ def demux(p, llr, cinit=None, words=None, erase_punctured=True):
     t = _lib.torch()
     t, llr, ld = _rows(llr, p.Gtotal, (t.float32, t.float64), "llr")
     T = llr.shape[0]
-    w = words if words is not None else (phy.prbs_words(cinit, p.Gtotal) if cinit is not None else None)
+    w = words if words is not None else (None if cinit is None else phy.prbs_words(cinit, p.Gtotal))
     if w is not None:
         assert w.dim() == 2 and w.shape[0] == T and w.stride(1) == 1 and w.shape[1] * 32 >= p.Gtotal
     outs = [t.empty((T, p.lens[n]), dtype=llr.dtype, device=llr.device) for n in STREAMS]
-    args = []
+    args = {}
     for n, o in zip(STREAMS, outs):
-        args += [_lib.ptr(o) if p.lens[n] else None, p.lens[n]]
-    with t.cuda.device(llr.device):
-        _lib.check(_lib.lib().ldpc5g_uci_demux(
-            _lib.ptr(p.dev(llr.device)), p.host, _lib.ptr(llr), _dt(t, llr.dtype), ld, _lib.ptr(w) if w is not None else None,
-            (w.stride(0) if T > 1 else w.shape[1]) if w is not None else 0, int(bool(erase_punctured)), *args, T,
-            _lib.stream_ptr()))
+        args["g_" + n], args["ld_" + n] = (o if p.lens[n] else None), p.lens[n]
+    _lib.call("ldpc5g_uci_demux", llr.device, plan_dev=p.dev(llr.device), plan_host=p.host, llr=llr,
+              dtype=_lib.dtype_id(llr.dtype), ldl=ld, prbs=w, ldw=_lib.row_stride(w, 0, w.shape[1]) if w is not None else 0,
+              erase_punctured=int(bool(erase_punctured)), **args, T=T)
     return UciStreams(*outs)
 
 
@@ -292,7 +277,6 @@ def scramble_modulate(g_seq, mod, cinit=None, words=None):
     w = words if words is not None else phy.prbs_words(cinit, G)
     assert w.dim() == 2 and w.shape[0] == T and w.stride(1) == 1 and w.shape[1] * 32 >= G
     sym = t.empty((T, G // Qm), dtype=t.complex64, device=g.device)
-    with t.cuda.device(g.device):
-        _lib.check(_lib.lib().ldpc5g_uci_scramble_modulate(_lib.ptr(g), ld, _lib.ptr(w), w.stride(0) if T > 1 else w.shape[1], T,
-                                                           G, int(mod), _lib.ptr(sym), G // Qm, _lib.stream_ptr()))
+    _lib.call("ldpc5g_uci_scramble_modulate", g.device, bits=g, ldb=ld, prbs=w, ldw=_lib.row_stride(w, 0, w.shape[1]), T=T,
+              nbits=G, mod=int(mod), sym=sym, ldsym=G // Qm)
     return sym

@@ -27,10 +27,11 @@ def _call(lib, y=P, ldy=None, h=P, ldh=None, cov=P, ldcov=None, dtype=_lib.F64, 
           rpc=12, T=2, Nr=4, NL=2, algo=3, sym=P, ldsym=None, nv=P, ldnv=None):
     nre = R if nre is None else nre
     ncov = -(-R // rpc) if rpc > 0 else 1
-    return lib.ldpc5g_equalize(
-        y, R * Nr if ldy is None else ldy, h, R * Nr * NL if ldh is None else ldh, cov,
-        ncov * Nr * Nr if ldcov is None else ldcov, dtype, re_idx, R, nre, rpc, T, Nr, NL, algo, sym,
-        nre * NL if ldsym is None else ldsym, nv, nre * NL if ldnv is None else ldnv, None)
+    return _lib.invoke(
+        "ldpc5g_equalize", y=y, ldy=R * Nr if ldy is None else ldy, h=h, ldh=R * Nr * NL if ldh is None else ldh,
+        cov=cov, ldcov=ncov * Nr * Nr if ldcov is None else ldcov, in_dtype=dtype, re_idx=re_idx, R=R, nre=nre,
+        re_per_cov=rpc, T=T, Nr=Nr, NL=NL, algo=algo, sym=sym, ldsym=nre * NL if ldsym is None else ldsym,
+        noise_var=nv, ldnv=nre * NL if ldnv is None else ldnv, stream=None)
 
 
 def _bad(lib, rc):

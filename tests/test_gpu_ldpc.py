@@ -559,6 +559,17 @@ def test_dlsch_encode_chain_with_gpu_encoder(torch, enc):
         assert np.array_equal(np.concatenate(out), g_ref)
 
 
+def test_dec_blocks_per_cu_diagnostic(torch):
+    """ldpc5g_dec_blocks_per_cu (no reference counterpart): the occupancy calculator's answer for
+    every decoder the other tests launch.  A kernel that launches at all fits a CU at least once,
+    and a CU holds 4 SIMDs x 8 waves = 32 waves, so at most 32 workgroups of one wave or more."""
+    from python_5gtoolbox_amd import _lib
+    for bgn in (1, 2):
+        for dt, sched in ((_lib.F32, _lib.FLOODING), (_lib.F64, _lib.FLOODING), (_lib.F32, _lib.LAYERED)):
+            n = _lib.invoke("ldpc5g_dec_blocks_per_cu", bgn=bgn, llr_dtype=dt, schedule=sched)
+            assert 1 <= n <= 32, (bgn, dt, sched, n)
+
+
 # ---------------------------------------------------------------------------------- BF / BP
 def test_decode_bf_golden_bitexact(torch, dec):
     """algo='BF' (ldpc_decoder_bit_flipping.py:5-73): ck (float64 like the reference) and status

@@ -33,6 +33,113 @@ def test_library_exports_every_declared_symbol():
     assert lib.ldpc5g_version().startswith(b"ldpc5g")
 
 
+def test_parameter_counts_match_header_for_every_function():
+    """The derived tables against a count taken independently of the binding's parser: the commas
+    of each prototype."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    names = declared_functions()
+    assert len(names) == 64
+    for n in names:
+        protos = re.findall(r"\b%s\s*\(([^)]*)\)\s*;" % n, src)
+        assert len(protos) == 1, n
+        count = 0 if protos[0].strip() == "void" else protos[0].count(",") + 1
+        assert len(_lib.PARAMS[n]) == count == len(_lib.SIGNATURES[n][1]), n
+
+
+def test_typed_anchors():
+    """Types written out by hand for prototypes that together hold every C type of the header."""
+    c = ctypes
+    i32, i64, dbl, ptr = c.c_int32, c.c_int64, c.c_double, c.c_void_p
+    anchors = {
+        "ldpc5g_sch_config": (c.c_int, [i32, i32, dbl, i32, i32, i64, i64, ptr],
+                              "A Qm coderateby1024 NL rv TBS_LBRM G cfg"),
+        "ldpc5g_ce_workspace_bytes": (i64, [i32] * 6, "T S N Nr Nt D"),
+        "ldpc5g_ofdm_mod": (c.c_int, [ptr, i64, i64, ptr, ptr, i64, i64, i32, i32, i32, i32, i32, i32, i64, ptr],
+                            "grid ld_g_slot ld_g_ant dm td ld_td_slot ld_td_ant dtype T num_ant nfft carrier_re scs "
+                            "carrier_hz stream"),
+        "ldpc5g_split_timeouts": (c.c_int, [ptr], "count"),
+        "ldpc5g_last_error": (c.c_char_p, [], ""),
+    }
+    for name, (res, args, params) in anchors.items():
+        assert _lib.SIGNATURES[name] == (res, args), name
+        assert _lib.PARAMS[name] == tuple(params.split()), name
+    lib = _lib.lib()
+    for name, (res, args) in _lib.SIGNATURES.items():   # and bind() put them on the handle
+        f = getattr(lib, name)
+        assert f.restype is res and list(f.argtypes) == args, name
+
+
+@pytest.mark.parametrize("text,line", [
+    ("/* c */\nint ldpc5g_a(int32_t n);\nint ldpc5g_b(int32_t n,\n  size_t m);\n", 3),    # unknown type
+    ("// c\n\nvoid ldpc5g_a(int32_t n);\n", 3),                                           # unknown return type
+    ("int ldpc5g_a(int32_t n);\nint ldpc5g_b(int32_t v[4]);\n", 2),                       # not `type name`
+])
+def test_header_parser_names_the_line_it_cannot_map(tmp_path, text, line):
+    h = tmp_path / "bad.h"
+    h.write_text(text)
+    with pytest.raises(ImportError, match=r"bad\.h:%d: ldpc5g_" % line):
+        _lib._parse_header(str(h))
+
+
+def test_invoke_refuses_wrong_keywords():
+    with pytest.raises(TypeError, match="zc"):
+        _lib.invoke("ldpc5g_find_ils", zc=8)
+    with pytest.raises(TypeError, match="extra"):
+        _lib.invoke("ldpc5g_find_ils", Zc=8, extra=1)
+    with pytest.raises(TypeError, match="Zc"):
+        _lib.invoke("ldpc5g_find_ils")
+    assert _lib.invoke("ldpc5g_find_ils", Zc=8) == _lib.lib().ldpc5g_find_ils(8) == ldpc_info.find_iLS(8)
+
+
+def test_keywords_reach_their_slots_through_the_abi():
+    """The valid ldpc5g_equalize call of tests/test_eq_host.py (T=2, R=72, Nr=4, NL=2), its keywords
+    in shuffled order: each single change is refused for its own reason."""
+    P = ctypes.c_void_p(4096)   # a non-null "buffer" (never dereferenced)
+    good = dict(y=P, ldy=72 * 4, h=P, ldh=72 * 4 * 2, cov=P, ldcov=6 * 16, in_dtype=_lib.F64, re_idx=None, R=72,
+                nre=72, re_per_cov=12, T=2, Nr=4, NL=2, algo=3, sym=P, ldsym=72 * 2, noise_var=P, ldnv=72 * 2,
+                stream=None)
+    assert set(good) == set(_lib.PARAMS["ldpc5g_equalize"])
+    keys = list(good)
+    np.random.default_rng(5).shuffle(keys)
+    assert keys != list(_lib.PARAMS["ldpc5g_equalize"])
+    for change, word in ((dict(y=None), b"null"), (dict(ldh=72 * 4 * 2 - 1), b"stride"), (dict(Nr=3), b"Nr")):
+        kw = {k: good[k] for k in keys}
+        kw.update(change)
+        assert _lib.invoke("ldpc5g_equalize", **kw) == _lib.ESIZE
+        assert word in _lib.lib().ldpc5g_last_error(), (change, _lib.lib().ldpc5g_last_error())
+        with pytest.raises(AssertionError, match=word.decode()):
+            _lib.call("ldpc5g_equalize", **kw)
+
+
+def test_invoke_converts_pointer_arguments():
+    """ldpc5g_sch_multi_sizes (host only) with `sizes` as a ctypes array, a numpy array and a CPU
+    torch tensor: the same seven numbers."""
+    import torch
+    from python_5gtoolbox_amd import sch
+    cfgs = [sch.sch_config(*a) for a in ((8000, 4, 700, 1, 3, 60000, 26000), (200, 2, 300, 1, 0, 60000, 2400))]
+    arr = (_lib.SchCfg * 2)(*cfgs)
+    ref = (ctypes.c_int64 * 7)()
+    assert _lib.invoke("ldpc5g_sch_multi_sizes", cfgs=arr, T=2, sizes=ref) == 0
+    assert list(ref)[3] == cfgs[0].C + cfgs[1].C and min(ref) > 0
+    a = np.zeros(7, np.int64)
+    assert _lib.call("ldpc5g_sch_multi_sizes", cfgs=arr, T=2, sizes=a) is None
+    assert a.tolist() == list(ref)
+    ro = np.frombuffer(bytes(arr), np.uint8)   # a read-only array
+    assert not ro.flags.writeable
+    assert _lib.invoke("ldpc5g_sch_multi_sizes", cfgs=ro, T=1, sizes=a) == 0
+    assert a[3] == cfgs[0].C and a[4] == cfgs[0].A
+    x = torch.zeros(7, dtype=torch.int64)
+    assert _lib.invoke("ldpc5g_sch_multi_sizes", cfgs=ctypes.byref(arr), T=2, sizes=x) == 0
+    assert x.tolist() == list(ref)
+
+
+def test_dec_blocks_per_cu_refuses_bad_base_graph():
+    """The one function no other test reached; its bgn check comes before the occupancy query."""
+    for bgn in (0, 3):
+        assert _lib.invoke("ldpc5g_dec_blocks_per_cu", bgn=bgn, llr_dtype=_lib.F32, schedule=_lib.LAYERED) == _lib.EBGN
+        assert b"bgn=%d" % bgn in _lib.lib().ldpc5g_last_error()
+
+
 def test_header_constants_match_binding():
     src = open(HEADER).read()
     consts = dict(re.findall(r"#define (LDPC5G_\w+) \(?(-?\d+)\)?", src))

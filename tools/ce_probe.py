@@ -161,9 +161,7 @@ def main():
     h_ls64 = torch.tensor(make_h_ls(T)).to(dev)
     lib_a, lib_b = _lib.lib(), None
     if args.lib_b:
-        lib_b = ctypes.CDLL(os.path.abspath(args.lib_b))
-        lib_b.ldpc5g_channel_estimate.restype, lib_b.ldpc5g_channel_estimate.argtypes = \
-            _lib.SIGNATURES["ldpc5g_channel_estimate"]
+        lib_b = _lib.bind(ctypes.CDLL(os.path.abspath(args.lib_b)))
 
     def raw_ce(lib, h_ls, algo, h, cov):
         """ldpc5g_channel_estimate of `lib` (a ctypes handle) on the current stream."""

@@ -82,8 +82,7 @@ def main():
     lib_a = _lib.lib()
     lib_b = None
     if args.lib_b:
-        lib_b = ctypes.CDLL(os.path.abspath(args.lib_b))
-        lib_b.ldpc5g_equalize.restype, lib_b.ldpc5g_equalize.argtypes = _lib.SIGNATURES["ldpc5g_equalize"]
+        lib_b = _lib.bind(ctypes.CDLL(os.path.abspath(args.lib_b)))
     gen = torch.Generator(device=dev)
     gen.manual_seed(36036)
 
