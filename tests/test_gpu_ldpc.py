@@ -1,12 +1,16 @@
 """GPU parity tests: the HIP kernels (through libldpc5g.so's C ABI) against the reference's golden
 vectors and the oracle.  Run on an MI355X with `pytest -m gpu`.
 
-Bars (DESIGN.md §5):
+Bars (DESIGN.md §2):
   encode ..................... bit-exact with the reference (all 51 Zc x 2 BG, fillers)
-  decode float64 flooding .... bit-exact ck + status with the reference (every fixture)
+  decode float64 flooding .... bit-exact ck + status with the reference (every fixture of
+                               decode_golden.npz: Zc <= 96 and three BG1 Zc = 384 codeblocks)
   decode float32 flooding .... bit-exact ck + status + iters with the fp32 oracle restatement
   decode float32 layered ..... bit-exact ck + status + iters with the layered oracle
   full-size (4096 x BG1 Zc=384): codeword syndrome == 0, encode->BPSK->decode round trip
+"All 51 Zc x 2 BG" holds here for encode only; the decoders meet hand-picked sizes in this file and
+all 102 pairs, path by path, in tests/test_gpu_ldpc_sweep.py (with the reference's outputs at
+Zc 104 ... 352 and BG2 Zc = 384 from decode_midzc_golden.npz).
 """
 import math
 import os

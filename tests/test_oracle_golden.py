@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLD, load_algo_cases, load_json, load_sparse_cases
+from ldpc_sweep_ref import MID, load_midzc_cases
 from oracle import ldpc_oracle as O
 
 
@@ -82,6 +83,37 @@ def test_decode_golden_z384(decode_cases, dtype):
         assert bool(st_k) == c["status"]
         if dtype == np.float64 or c["status"]:
             assert np.array_equal(ck_k, c["ck"])
+
+
+def test_decode_midzc_golden_fp64():
+    """float64 restatement == reference nr_decode_ldpc (ck and status) at the lifting sizes the
+    other decode fixtures leave out: every Zc in 104 ... 352 of both base graphs and BG2 Zc = 384,
+    one NMS and one OMS codeblock each, half of them with a zeroed tail, on quarter-step LLRs
+    (tests/golden/decode_midzc_golden.npz)."""
+    cases = load_midzc_cases("min-sum")
+    assert len(cases) == 62
+    assert {(c["bg"], c["Zc"]) for c in cases} == {(bg, z) for bg in (1, 2) for z in MID} | {(2, 384)}
+    assert {(c["alpha"], c["beta"]) for c in cases} == {(0.75, 0.0), (1.0, 0.5)}
+    assert sum(c["nzero"] > 0 for c in cases) == 31 and all(c["L"] == 8 for c in cases)
+    n_true = sum(c["status"] for c in cases)
+    assert 25 <= n_true <= 37                                    # about half converge
+    for c in cases:
+        assert not c["nzero"] or not c["llr"][-c["nzero"] * c["Zc"]:].any()
+        ck, st, _ = O.decode_flooding(c["llr"][None], c["Zc"], c["bg"], c["L"], c["alpha"], c["beta"], np.float64)
+        assert np.array_equal(ck[0], c["ck"]) and bool(st[0]) == c["status"], (c["bg"], c["Zc"], c["alpha"])
+
+
+@pytest.mark.parametrize("algo", ["BF", "BP"])
+def test_bf_bp_midzc_golden(algo):
+    """decode_bf / decode_bp == the reference's algo='BF' / 'BP' at four mid lifting sizes, bit
+    for bit, as test_bf_bp_golden asks at the small ones."""
+    fn = O.decode_bf if algo == "BF" else O.decode_bp
+    cases = load_midzc_cases(algo)
+    assert [(c["bg"], c["Zc"]) for c in cases] == [(1, 104), (2, 144), (1, 208), (2, 352)]
+    assert {c["status"] for c in cases} == {True, False}
+    for c in cases:
+        ck, st, _ = fn(c["llr"][None], c["Zc"], c["bg"], c["L"])
+        assert np.array_equal(ck[0], c["ck"]) and bool(st[0]) == c["status"], (c["bg"], c["Zc"])
 
 
 def test_layered_agrees_at_high_snr():
